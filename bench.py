@@ -24,10 +24,14 @@ host's entry point, its own RCCL communicator); --torch-router runs the round-2 
 api-ratelimit_amd/router.py (torch.distributed) instead. value = descriptors decided for all ranks / max-over-ranks time.
 --independent runs N unrouted replicas instead (each rank its own key space).
 
-Also reported (rank 0): per-kernel HIP-event times over an extra K steps, the roofline of the
-dominant kernel and the SURVEY §8(d) random-access roofline, table occupancy, the host
+A plain run sets up, prefills, warms up, times --steps steps and prints the result line
+(ms_per_step = the time of one timed step); --dump-outputs DIR also writes what the last timed
+step returned (the inputs are seeded: the same arguments give the same arrays on every run).
+
+--full also reports (rank 0): per-kernel HIP-event times over an extra K steps, the roofline
+of the dominant kernel and the SURVEY §8(d) random-access roofline, table occupancy, the host
 (PCIe) path end to end, and the CPU oracle timed on a bounded sample of the same stream on
-1 and on N host threads (cpu_baseline).
+1 and on N host threads (cpu_baseline). Without it those fields of the line are null.
 """
 from __future__ import annotations
 
@@ -92,11 +96,19 @@ def parse():
     ap.add_argument("--log2-slots", type=int, default=27,
                     help="table slots per region (home unit x parity); 2^27 x 32 B x 6 regions = 25.8 GB, ~23 %% load "
                          "at config 3's live set (shorter probe chains than 2^26 at ~46 %%)")
-    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU baseline sample budget per leg (0 = skip)")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="N-thread CPU baseline (0 = min(16, cpus))")
-    ap.add_argument("--no-kernel-times", action="store_true")
-    ap.add_argument("--no-roofline-probe", action="store_true")
-    ap.add_argument("--no-host-path", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: per-kernel times "
+                         "and the roofline, the random-access probe, table occupancy, the host (PCIe) path and the CPU "
+                         "baseline (each can be switched off below); without it those fields of the line are null")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step returned (descriptor statuses, "
+                         "ThrottleMillis) to DIR/<name>.npy as float64, at most 64 MB in all")
+    ap.add_argument("--cpu-seconds", type=float, default=8.0,
+                    help="--full: CPU baseline sample budget per leg (0 = skip)")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="--full: N-thread CPU baseline (0 = min(16, cpus))")
+    ap.add_argument("--no-kernel-times", action="store_true", help="--full without the per-kernel times and roofline")
+    ap.add_argument("--no-roofline-probe", action="store_true", help="--full without the random-access probe")
+    ap.add_argument("--no-host-path", action="store_true", help="--full without the host (PCIe) path")
     ap.add_argument("--host-formats", default="compact,full", help=argparse.SUPPRESS)  # traces: one format only
     ap.add_argument("--host-no-probe", action="store_true", help=argparse.SUPPRESS)  # traces: no link probes
     ap.add_argument("--pipeline", choices=["v4", "lsd"], default="v4",
@@ -323,6 +335,33 @@ class HostGen:
 
     def make(self, b: int):
         return _router().DeviceBatch.from_host(workload.config1_batch(b, d=self.d, seed=self.seed, t0=T0), self.dev)
+
+
+DUMP_ROWS = 1_000_000  # x (5 status fields + ThrottleMillis) x 8 B = 48 MB, + 8 MB of sample indices
+
+
+def dump_outputs(path, out, d, rank, world):
+    """--dump-outputs: what the caller of the timed path received from its last step, as float64
+    (every field is a u32, exact in float64): status.npy [n, 5] (code_flags, limit_remaining,
+    reset_s, over_limit_delta, near_limit_delta per descriptor) and throttle_ms.npy [n] (per
+    request; one descriptor per request in every bench workload). Batches above DUMP_ROWS
+    descriptors are written as a fixed seeded sample of rows, its indices in sample_index.npy.
+    Ranks above 0 of a multi-GPU run write <name>_rank<r>.npy."""
+    st, thr = out
+    st = st.cpu().numpy()[:d * 20].view(np.uint32).reshape(d, 5)
+    thr = thr.cpu().numpy()[:d].view(np.uint32)
+    arrays = {}
+    if d > DUMP_ROWS:
+        idx = np.sort(np.random.default_rng(0x0D0C).choice(d, DUMP_ROWS, replace=False))
+        st, thr = st[idx], thr[idx]
+        arrays["sample_index"] = idx.astype(np.float64)
+    arrays["status"] = st.astype(np.float64)
+    arrays["throttle_ms"] = thr.astype(np.float64)
+    dst = Path(path)
+    dst.mkdir(parents=True, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 and rank else ""
+    for name, a in arrays.items():
+        np.save(dst / f"{name}{sfx}.npy", a)
 
 
 def random_access_roofline(eng, alg_bytes, U, pipe_ms, step_ms):
@@ -596,6 +635,7 @@ def main():
     thrs = [torch.empty(d, dtype=torch.int32, device=dev) for _ in range(hiprl.MAX_IN_FLIGHT)]
 
     host_t = {"submit": [], "wait": [], "step": []}  # host seconds per engine call / per loop step (pipelined)
+    torch_out = []  # --torch-router: the (statuses, ThrottleMillis) tensors its last step returned
 
     def run(dbs, first=0, depth=None):
         """One step per batch. Pipelined: batch k+1 is submitted before batch k is waited for (the
@@ -614,7 +654,7 @@ def main():
             eng.resolve_device(gen.resolve_struct(dbs[0]), dbs[0].rule.data_ptr())
         for j, db in enumerate(dbs):
             if rtr is not None:
-                rtr.step(db)
+                torch_out[:] = rtr.step(db)
                 continue
             if late and args.config == 4 and nrt is None:
                 eng.resolve_device(gen.resolve_struct(db), db.rule.data_ptr())
@@ -688,27 +728,53 @@ def main():
     t_fill = time.time() - t_fill
     fallbacks_prefill = eng.stats()["lsd_fallbacks"]
     # Timed batches (and warmup and kernel-timing batches) resident before timing.
-    n_kt = 0 if args.no_kernel_times else args.steps
+    # At most RESIDENT batches (~42 MB each at 1e6 descriptors) are held at a time: a longer run is
+    # made and timed in spans of that many steps, the clock stopped while the next span's batches
+    # are generated (the batches in flight complete at the end of every span).
+    RESIDENT = 256
+    n_kt = min(args.steps, RESIDENT) if args.full and not args.no_kernel_times else 0
     b0 = prefill
-    dbs = [gen.make(b0 + j) for j in range(args.warmup + args.steps + n_kt)]
-    torch.cuda.synchronize()
-    if args.config == 4 and (nrt is not None or rtr is not None):
-        for db in dbs:  # routed: rule ids resolved before timing (the N = 1 line resolves inside the step)
-            eng.resolve_device(gen.resolve_struct(db), db.rule.data_ptr())
+    n_all = args.warmup + args.steps + n_kt
+
+    def resident(lo, hi):
+        """Batches b0 + lo .. b0 + hi - 1 of the stream, generated and complete on the device."""
+        made = [gen.make(b0 + j) for j in range(lo, hi)]
         torch.cuda.synchronize()
-    run(dbs[:args.warmup])
+        if args.config == 4 and (nrt is not None or rtr is not None):
+            for db in made:  # routed: rule ids resolved before timing (the N = 1 line resolves inside the step)
+                eng.resolve_device(gen.resolve_struct(db), db.rule.data_ptr())
+            torch.cuda.synchronize()
+        return made
+
+    dbs = resident(0, n_all) if n_all <= RESIDENT else None  # (the usual case: everything made up front)
+
+    def span(lo, hi):
+        return dbs[lo:hi] if dbs is not None else resident(lo, hi)
+
+    for lo in range(0, args.warmup, RESIDENT):
+        run(span(lo, min(lo + RESIDENT, args.warmup)), lo)
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
     fb0 = eng.stats()["lsd_fallbacks"]
     for v in host_t.values():
         v.clear()
-    t0 = time.perf_counter()
-    run(dbs[args.warmup:args.warmup + args.steps], args.warmup)
-    torch.cuda.synchronize()
-    if dist:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = 0.0
+    timed = []
+    for lo in range(args.warmup, args.warmup + args.steps, RESIDENT):
+        timed = None  # (the span before this one is released before the next is made)
+        timed = span(lo, min(lo + RESIDENT, args.warmup + args.steps))
+        if dist:
+            dist.barrier()
+        t0 = time.perf_counter()
+        run(timed, lo)
+        torch.cuda.synchronize()
+        if dist:
+            dist.barrier()
+        elapsed += time.perf_counter() - t0
+    if args.dump_outputs:
+        last = (args.warmup + args.steps - 1) % hiprl.MAX_IN_FLIGHT
+        dump_outputs(args.dump_outputs, torch_out if rtr is not None else (outs[last], thrs[last]), d, rank, world)
     # (outside the timed region)
     host_us = {k: {"mean": round(sum(v) / max(1, len(v)) * 1e6, 1),
                    "p50": round(float(np.median(v)) * 1e6, 1) if v else None,
@@ -728,9 +794,10 @@ def main():
     # Per-kernel HIP-event timing over another K steps of the same stream (one stream, unoverlapped).
     kernel, uniq = None, []
     if n_kt:
+        kdbs = span(args.warmup + args.steps, n_all)
         eng.set_timing(True)
-        for j in range(args.warmup + args.steps, len(dbs)):
-            run([dbs[j]], j)
+        for j, db in enumerate(kdbs, args.warmup + args.steps):
+            run([db], j)
             uniq.append(eng.last_batch_info()["unique_keys"])
         kt = eng.kernel_times()
         eng.set_timing(False)
@@ -743,7 +810,7 @@ def main():
         eng.lib.rl_debug_st4(st4.ctypes.data)
         np.save(args.dump_stamps, st4)
     stats = eng.stats()
-    occ = eng.occupancy()
+    occ = eng.occupancy() if args.full else None
 
     # Host (PCIe) path (what a Go service sees: host batches, three in flight), in the compact
     # wire format (rl_batch_c: prefix bytes + one word per descriptor + one per request in, 8-B
@@ -760,9 +827,9 @@ def main():
     #    descriptor on 1 thread and desc/s on `threads` threads splitting each batch;
     #  - frac_of_pcie_bound = that bound / the measured per-batch time.
     host = None
-    if not args.no_host_path and not routed:
+    if args.full and not args.no_host_path and not routed:
         hbatches = []
-        for db in dbs[args.warmup:args.warmup + args.steps]:
+        for db in timed[:32]:  # (of the last span of timed steps; three of them are staged below)
             n = int(db.off[-1].item())
             hbatches.append(hiprl.Batch(db.blob[:n].cpu().numpy(), db.off.cpu().numpy().view(np.uint32),
                                         db.rule.cpu().numpy().view(np.uint32), db.req_of.cpu().numpy().view(np.uint32),
@@ -931,7 +998,7 @@ def main():
         return
 
     U = float(np.mean(uniq))
-    nbytes = int(dbs[-1].off[-1].item())
+    nbytes = int((kdbs if n_kt else timed)[-1].off[-1].item())
     alg_bytes = nbytes + 12 * d + 12 * d + 20 * d + 4 * d + 64 * int(U)  # workload.algorithmic_bytes, r = d
     alg_def = ("achieved = algorithmic bytes of one batch (SURVEY §8d: prefixes + 12 B/desc + 16 B/req + 20 B/desc out "
                "+ 64 B per unique key) / the dominant kernel's average launch time (HIP events on the engine stream, "
@@ -958,7 +1025,7 @@ def main():
                    "launch time on that batch (HIP events, unoverlapped); not a whole-batch figure")
     roofline = None
     if kernel:
-        per_batch_ms = {k: v["total_ms"] / args.steps for k, v in kernel.items()}
+        per_batch_ms = {k: v["total_ms"] / n_kt for k, v in kernel.items()}
         pipe_ms = sum(per_batch_ms.values())
         dom = max((k for k in per_batch_ms if k != "memset"), key=lambda k: per_batch_ms[k])
         dom_us = kernel[dom]["total_ms"] * 1e3 / kernel[dom]["launches"]
@@ -990,10 +1057,10 @@ def main():
                 roofline["random_access"] = ra
 
     cpu = None
-    if world == 1 and args.cpu_seconds > 0:
+    if args.full and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(args, rules, d, seed, K, b0, eng)
 
-    live_frac = [round(occ["live"][r] / occ["slots"][r], 4) for r in range(8)]
+    live_frac = [round(occ["live"][r] / occ["slots"][r], 4) for r in range(8)] if occ else None
     if routed and nrt is not None:
         parallelism = (f"key-sharded x{world}, RCCL all-to-all routing through the C-ABI router (32-B records out, one "
                        f"per hot key per origin with combining; 8-B raw replies back; {RDEPTH} steps in flight)")
@@ -1028,8 +1095,9 @@ def main():
         "router": ({k: rstats[k] for k in ("recv", "sent", "combined", "combined_steps", "repacks", "hot_groups",
                                            "pack_us", "exchange_us", "decide_us", "reply_us", "unpack_us", "step_us")}
                    if rstats else None),
-        "table": {"live_keys": stats["live_keys"], "region_live_fraction": live_frac, "region_slots": occ["slots"],
-                  "bytes": int(sum(occ["slots"])) * 32},
+        "table": {"live_keys": stats["live_keys"], "region_live_fraction": live_frac,
+                  "region_slots": occ["slots"] if occ else None,
+                  "bytes": int(sum(occ["slots"])) * 32 if occ else None},
         "engine": {"resorts": stats["resorts"], "lsd_fallbacks_prefill": fallbacks_prefill,
                    "lsd_fallbacks_timed": fb_timed, "hot_keys": stats["hot_keys"], "batches": stats["batches"],
                    "prefill_s": round(t_fill, 1), "source_sha": source_sha(),

@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 for t in $vars; do
   IFS=, read -r lib envs <<< "$t"
   [ "$lib" = "-" ] && lib=""
-  env ${envs//,/ } timeout -k 10 150 python bench.py --steps "$steps" --warmup 30 --cpu-seconds 0 --no-roofline-probe \
+  env ${envs//,/ } timeout -k 10 150 python bench.py --full --steps "$steps" --warmup 30 --cpu-seconds 0 --no-roofline-probe \
     --no-host-path ${lib:+--lib $lib} "$@" > gpurun_out/ab.log 2>&1 || { tail -5 gpurun_out/ab.log; exit 1; }
   python - "$t" <<'PY'
 import json, sys

@@ -21,15 +21,15 @@ case $PART in
        "240:python -u -c 'import __graft_entry__ as g; g.smoke()'" \
        "500:bash tools/pmc_round.sh ${TAG}_c3 20 '' 3" \
        "30:$(cp_pmc ${TAG}_c3 r06_pmc_traffic.json)" \
-       "400:python -u bench.py > gpurun_out/${TAG}A/bench_c3.json" \
-       "400:python -u bench.py > gpurun_out/${TAG}A/bench_c3_b.json" ;;
+       "400:python -u bench.py --full > \$OUT/bench_c3.json" \
+       "400:python -u bench.py --full > \$OUT/bench_c3_b.json" ;;
   B) bash tools/gpu_steps.sh "${TAG}B" \
        "500:bash tools/pmc_round.sh ${TAG}_c4 20 '' 4" \
        "30:$(cp_pmc ${TAG}_c4 r06_pmc_traffic_config4.json)" \
-       "400:python -u bench.py --config 4 > gpurun_out/${TAG}B/bench_c4.json" \
+       "400:python -u bench.py --full --config 4 > \$OUT/bench_c4.json" \
        "500:bash tools/pmc_round.sh ${TAG}_c5 20 '' 5" \
        "30:$(cp_pmc ${TAG}_c5 r06_pmc_traffic_config5.json)" \
-       "400:python -u bench.py --config 5 > gpurun_out/${TAG}B/bench_c5.json" ;;
+       "400:python -u bench.py --full --config 5 > \$OUT/bench_c5.json" ;;
   C) bash tools/gpu_steps.sh "${TAG}C" "500:bash tools/pmc_routed.sh ${TAG}_routed 30" &&
      bash tools/gpu_bench_round.sh "${TAG}C" "routed1 ls2 ls4 ls8 config1" ;;
 esac

@@ -25,6 +25,6 @@ stop_on_crash $? pytest
 tail -5 "$OUT/pytest.log"
 timeout -k 10 240 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
 stop_on_crash $? smoke
-timeout -k 10 600 python -u bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 600 python -u bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
 stop_on_crash $? bench
 cat "$OUT/bench.json"

@@ -11,6 +11,7 @@ TAG=$1
 shift
 OUT=${GRAFT_REPO_ROOT:-$(pwd)}/gpurun_out/$TAG
 mkdir -p "$OUT"
+export OUT  # a step may write its own files there
 i=0
 for step in "$@"; do
   i=$((i + 1))

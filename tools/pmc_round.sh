@@ -22,7 +22,7 @@ cd /tmp && export TMPDIR=/tmp
 BENCH="python3 $R/bench.py --config $CFG --steps $STEPS --warmup 3 --cpu-seconds 0 --no-kernel-times --no-roofline-probe --no-host-path"
 # the trace run keeps bench.py's unoverlapped kernel-timing batches (the last STEPS dispatches)
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $P/trace -o run --output-format csv -- \
-  python3 $R/bench.py --config $CFG --steps $STEPS --warmup 3 --cpu-seconds 0 --no-roofline-probe --no-host-path \
+  python3 $R/bench.py --full --config $CFG --steps $STEPS --warmup 3 --cpu-seconds 0 --no-roofline-probe --no-host-path \
   > "$OUT/trace.json" 2> "$OUT/trace.err" || { echo "trace rc=$?"; tail -5 "$OUT/trace.err"; exit 1; }
 cp $P/trace/run_kernel_stats.csv "$OUT/kernel_stats.csv"
 python3 $R/tools/trace_summary.py $P/trace/run_kernel_trace.csv "$OUT/trace.json" $STEPS "$OUT/kernel_trace_summary.json" > /dev/null
