@@ -224,7 +224,9 @@ struct EngineCtl {
   uint32_t tile_ctr[32][64];  // dynamic tile tickets / hand-off counters, one 256-B line each
 };
 static_assert(sizeof(EngineCtl) == 256 + 32 * 256, "EngineCtl layout");
-// tile_ctr rows 16..23: per-region new-slot counters of the LSD leader (row INS_CTR0 + region)
+// tile_ctr rows 16..23: per-region new-slot counters of the LSD leader (row INS_CTR0 + region).
+// The v4 pipeline's control blocks use rows 0..7 (blocks done per shard), 8..15 (the batch's key
+// and new-slot sums per shard, SUM_CTR0 in rl_kernels_v4.hip), 27 (DONE_CTR), DFR_CTR and CAND_CTR.
 constexpr int INS_CTR0 = 16;
 constexpr int INS_LINES = 8;
 

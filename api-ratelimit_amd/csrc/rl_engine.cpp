@@ -58,23 +58,20 @@ uint32_t compact_chunks(uint32_t n);
 void launch_compact_expand(hipStream_t, uint32_t, uint32_t, int64_t, const uint32_t*, const uint32_t*, const uint32_t*,
                            uint32_t*, uint32_t*, uint32_t*, uint32_t*, int64_t*, uint32_t*);
 uint32_t v4_tiles(uint32_t n);
-uint32_t v4_group_blocks(uint32_t n);
-uint32_t v4_scan_blocks();
 size_t v4_scratch_bytes();
 void launch_v4_hist(hipStream_t, const rl_batch&, const DevRule*, uint32_t, uint64_t, const HotEntry*, uint32_t*,
                     uint32_t*, uint16_t*, unsigned long long*, MRec*, rl_status*, EngineCtl*);
 void launch_v4_scan(hipStream_t st, uint32_t n, const uint16_t* tstart, const unsigned long long* thsum,
                     unsigned long long* hoff, const uint32_t* fpart, const HotEntry* hot_list, HotBucket* hb,
-                    const TableDesc& tab, HotCand* cand, uint32_t* heads_out, uint32_t* ins_out, void* scratch,
-                    const uint32_t* poison, const RegionOcc* occ, EngineCtl* ctl);
+                    const TableDesc& tab, HotCand* cand, void* scratch, const uint32_t* poison, const RegionOcc* occ,
+                    EngineCtl* ctl);
 void launch_v4_place(hipStream_t st, const rl_batch& b, const MRec* srec, const uint16_t* tstart,
                      void* scratch, const DevRule* rules, uint32_t n_rules, const unsigned long long* hoff, HotBucket* hb,
                      int local_cache, rl_status* out, uint32_t* req_thr, Deferred* dfr, int routed,
                      uint32_t* poison, EngineCtl* ctl);
 void launch_v4_group(hipStream_t st, const rl_batch& b, const DevRule* rules, uint32_t n_rules, const TableDesc& tab,
                      rl_status* out, uint32_t* req_thr, const HotBucket* hb, const Deferred* dfr, HotCand* cand,
-                     int cand_on, uint64_t seed, void* scratch, uint32_t* wg_heads, uint32_t* wg_ins,
-                     const uint32_t* scan_heads, const uint32_t* scan_ins, int routed, RegionOcc* occ, EngineCtl* ctl,
+                     int cand_on, uint64_t seed, void* scratch, int routed, RegionOcc* occ, EngineCtl* ctl,
                      EngineCtl* next_ctl, EngineCtl* hctl, HotCand* hcand, const MRec* srec,
                      const uint16_t* tstart);
 }  // namespace rlhip
@@ -191,8 +188,6 @@ struct rl_engine {
   Deferred* v4_dfr = nullptr;                 // deferred hot descriptors
   HotBucket* v4_hb = nullptr;                 // per hot bucket batch state
   void* v4_scratch = nullptr;                 // k4_group global scratch + k4_scan ranges
-  uint32_t* v4_heads = nullptr;               // per-block unique-key counts (k4_group, then k4_scan)
-  uint32_t* v4_ins = nullptr;                 // per-block new slots per region, 16-bit pairs (k4_group, then k4_scan)
   EngineCtl* v4_ctl[3] = {};                  // control blocks rotate over three (k4_group clears batch k+2's)
   uint32_t* d_poison = nullptr;               // set by k4_place of a refused batch, read by k4_scan
 
@@ -442,7 +437,6 @@ int rl_engine::run_pipeline(const rl_batch& b, rl_status* out, uint32_t* thr, in
     }
     const HotEntry* hot_t = d_hot;
     const int lc = cfg.local_cache ? 1 : 0;
-    const uint32_t ng = v4_group_blocks(n);
     MRec* srt = v4_srt[sl];
     timed(KT_V4_HIST, [&] {
       launch_v4_hist(fs, b, d_rules, n_rules, cfg.hash_seed, hot_t, thr, v4_fpart[sl], v4_tcount[sl], v4_thsum[sl],
@@ -454,8 +448,7 @@ int rl_engine::run_pipeline(const rl_batch& b, rl_status* out, uint32_t* thr, in
     }
     timed(KT_V4_SCAN, [&] {
       launch_v4_scan(stream, n, v4_tcount[sl], v4_thsum[sl], v4_hoff, v4_fpart[sl], hot_t + HOT_SLOTS, v4_hb, tab,
-                     want_cand ? d_cand : nullptr, v4_heads + ng, v4_ins + (size_t)ng * 4, v4_scratch, d_poison,
-                     d_occ, c4);
+                     want_cand ? d_cand : nullptr, v4_scratch, d_poison, d_occ, c4);
     });
     timed(KT_V4_PLACE, [&] {
       launch_v4_place(stream, b, srt, v4_tcount[sl], v4_scratch, d_rules, n_rules, v4_hoff, v4_hb, lc, out,
@@ -463,8 +456,7 @@ int rl_engine::run_pipeline(const rl_batch& b, rl_status* out, uint32_t* thr, in
     });
     timed(KT_V4_GROUP, [&] {
       launch_v4_group(stream, b, d_rules, n_rules, tab, out, thr, v4_hb, v4_dfr, d_cand, want_cand ? 1 : 0,
-                      cfg.hash_seed, v4_scratch, v4_heads, v4_ins, v4_heads + ng, v4_ins + (size_t)ng * 4, routed,
-                      d_occ, c4, c4n, h_ctl, want_cand ? h_cand : nullptr, srt, v4_tcount[sl]);
+                      cfg.hash_seed, v4_scratch, routed, d_occ, c4, c4n, h_ctl, want_cand ? h_cand : nullptr, srt, v4_tcount[sl]);
     });
     // k4_group's last block writes the summary into h_ctl / h_cand (pinned host memory)
     e = hipGetLastError();
@@ -1032,9 +1024,6 @@ int rl_create(const rl_config* cfg_in, rl_engine** out) {
     chk(hipMalloc(&e->v4_dfr, N * sizeof(Deferred) + 64));
     // the buckets, then per bucket the freezing request's last INCRBY (index, jitter): hot_exp()
     chk(hipMalloc(&e->v4_hb, HOT_BUCKETS * (sizeof(HotBucket) + 8)));
-    const size_t nb = (size_t)v4_group_blocks((uint32_t)N) + v4_scan_blocks();
-    chk(hipMalloc(&e->v4_heads, nb * 4 + 64));
-    chk(hipMalloc(&e->v4_ins, nb * 4 * 4 + 64));
     chk(hipMalloc(&e->v4_scratch, v4_scratch_bytes()));
     for (int k = 0; k < 3; ++k) {
       chk(hipMalloc(&e->v4_ctl[k], sizeof(EngineCtl)));
@@ -1107,7 +1096,7 @@ void rl_destroy(rl_engine* e) {
   }
   for (int k = 0; k < 3; ++k) hipFree(e->v4_ctl[k]);
   for (void* p : {(void*)e->v4_hoff, (void*)e->v4_dfr, (void*)e->v4_hb,
-                  (void*)e->v4_heads, (void*)e->v4_ins, e->v4_scratch, (void*)e->d_poison, (void*)e->d_tree_nodes,
+                  e->v4_scratch, (void*)e->d_poison, (void*)e->d_tree_nodes,
                   (void*)e->d_tree_slots, (void*)e->d_tree_names, (void*)e->d_tree_fnodes, (void*)e->d_tree_fslots, (void*)e->d_res, (void*)e->d_res_flags, (void*)e->table, (void*)e->d_occ,
                   (void*)e->d_rules, (void*)e->keys_orig, (void*)e->keys_a, (void*)e->keys_b, (void*)e->vals_a,
                   (void*)e->vals_b, (void*)e->recs, (void*)e->srec, (void*)e->seg, (void*)e->offs,

@@ -154,6 +154,24 @@ RL_DEV uint32_t* hot_counter(const HotBucket& x) {
   return (x.flags & HB_PS) ? &s->pcount : &s->count;
 }
 constexpr int SHARD_CTR0 = 0;  // EngineCtl::tile_ctr[0..7][0]: k4_group blocks done, by blockIdx & 7
+// EngineCtl::tile_ctr[SUM_CTR0 + (blockIdx & 7)]: the batch's sums over the k4_group blocks and
+// k4_scan's hot blocks of a shard. Word SUM_KEYS: keys led; u64 at word SUM_INS + 2x: new slots
+// of regions 2x (low half) and 2x + 1 (a batch has fewer than 2^32 descriptors: no carry).
+// Words [0, SUM_WORDS) of a row are read by the last k4_group block; the rest stay zero.
+constexpr int SUM_CTR0 = 8;
+constexpr int SUM_KEYS = 0, SUM_INS = 2, SUM_WORDS = 16;
+static_assert(SUM_CTR0 >= SHARD_CTR0 + 8 && SUM_CTR0 + 8 <= DONE_CTR && SUM_CTR0 + 8 <= DFR_CTR &&
+                  SUM_CTR0 + 8 <= CAND_CTR && SUM_INS % 2 == 0 && SUM_INS + 8 <= SUM_WORDS && SUM_WORDS <= 64,
+              "sum counter rows");
+// One lane per block, before the block's s_waitcnt vmcnt(0) / the kernel's end: agent-scope
+// adds without a return value, only of what is not zero.
+RL_DEV void add_block_sums(EngineCtl* ctl, uint32_t block, uint32_t keys, const uint64_t (&pair)[4]) {
+  uint32_t* row = ctl->tile_ctr[SUM_CTR0 + (block & 7u)];
+  if (keys) atomicAdd(&row[SUM_KEYS], keys);
+#pragma unroll
+  for (int x = 0; x < 4; ++x)
+    if (pair[x]) atomicAdd(reinterpret_cast<unsigned long long*>(&row[SUM_INS + 2 * x]), (unsigned long long)pair[x]);
+}
 
 // ---------------------------------------------------------------------------
 // k4_hist
@@ -490,7 +508,6 @@ __global__ __launch_bounds__(SCAN_NT) void k4_scan(const uint16_t* __restrict__ 
                                                    const uint32_t* __restrict__ fpart,
                                                    const HotEntry* __restrict__ hot_list, HotBucket* __restrict__ hb,
                                                    TableDesc tab, HotCand* __restrict__ cand,
-                                                   uint32_t* __restrict__ heads_out, uint32_t* __restrict__ ins_out,
                                                    uint32_t* __restrict__ ranges,
                                                    const uint32_t* __restrict__ poison,
                                                    const RegionOcc* __restrict__ occ, EngineCtl* ctl) {
@@ -653,7 +670,6 @@ __global__ __launch_bounds__(SCAN_NT) void k4_scan(const uint16_t* __restrict__ 
     // over BUCKET_CAP records sends the batch to the LSD pipeline before the table is touched.)
     if (wave != 0) return;
     ST5(3);
-    if (lane == 0) heads_out[blockIdx.x] = 0;
     if (ctot > (uint32_t)BUCKET_CAP) atomicOr(&ctl->err, ERR_FALLBACK);
     const uint32_t g = m;
     // Pack the group's 64 buckets into k4_group ranges of whole buckets, at most G_CAP records
@@ -816,20 +832,21 @@ __global__ __launch_bounds__(SCAN_NT) void k4_scan(const uint16_t* __restrict__ 
         }
       }
     }
-    // new slots per region of this block, two 16-bit counts a word (the last k4_group block
-    // adds them to RegionOcc)
+    // new slots per region and keys led by this block, into the batch's sum counters (the last
+    // k4_group block adds them to RegionOcc; also for a batch refused later on)
+    uint64_t pair[4];
 #pragma unroll
     for (int x = 0; x < 4; ++x) {
       const uint32_t lo_n = (uint32_t)__popcll(__ballot(ins_region == (uint32_t)(2 * x)));
       const uint32_t hi_n = (uint32_t)__popcll(__ballot(ins_region == (uint32_t)(2 * x + 1)));
-      if (lane == 0) ins_out[blockIdx.x * 4 + x] = lo_n | (hi_n << 16);
+      pair[x] = (uint64_t)lo_n | ((uint64_t)hi_n << 32);
     }
     if (lane < (uint32_t)HOT_PER_BLOCK) {
       hb[b] = x;
       if (local_cache) hot_exp(hb)[b] = 0;  // the freezing request's last INCRBY: (index, jitter), k4_place / k4_group
     }
     heads = tile::wave_sum(heads);
-    if (lane == 0) heads_out[blockIdx.x] = heads;
+    if (lane == 0) add_block_sums(ctl, blockIdx.x, heads, pair);
     ST5(4);
   }
 }
@@ -1404,11 +1421,7 @@ __global__ __launch_bounds__(G_NT, RL_G_OCC) void k4_group(DevBatch in,
                                                  rl_status* __restrict__ out, uint32_t* __restrict__ req_thr,
                                                  const HotBucket* __restrict__ hb, const Deferred* __restrict__ dfr,
                                                  HotCand* __restrict__ cand, int cand_on, uint64_t seed,
-                                                 GScratch4 gs, uint32_t* __restrict__ wg_heads,
-                                                 uint32_t* __restrict__ wg_ins,
-                                                 const uint32_t* __restrict__ scan_heads,
-                                                 const uint32_t* __restrict__ scan_ins, uint32_t n_scan_heads,
-                                                 const uint32_t* __restrict__ ranges, int routed,
+                                                 GScratch4 gs, const uint32_t* __restrict__ ranges, int routed,
                                                  RegionOcc* __restrict__ occ, EngineCtl* ctl, EngineCtl* next_ctl,
                                                  EngineCtl* hctl, HotCand* hcand,
                                                  const MRec* __restrict__ srec, const uint16_t* __restrict__ tstart,
@@ -1458,34 +1471,7 @@ __global__ __launch_bounds__(G_NT, RL_G_OCC) void k4_group(DevBatch in,
 #ifdef RL_STAMPS
   if (tid == 0 && j < 1024) for (int k = 0; k < 8; ++k) g_st4[3072 + j][k] = 0;  // this batch's facts only
 #endif
-  if (s_err == 0 && j < (uint32_t)(HOT_BUCKETS / G_NT)) {
-    // Hot keys (decided by k4_place) that no request froze: EXPIRE from the time and jitter of
-    // the last INCRBY (fixed_cache_impl.go:69-72). A key frozen in this batch gets its EXPIRE and
-    // freecache TTLs in the last block, once the deferred hot descriptors below have recorded
-    // which INCRBY of the freezing request came last.
-    const HotBucket x = hb[j * G_NT + tid];
-    if (x.slot && !(x.flags & (HB_FROZEN_PRE | HB_PS)) && x.rstar == 0xFFFFFFFFu) {
-      Slot* sl = reinterpret_cast<Slot*>(x.slot);
-      sl->exp = x.t_all + rules[x.rule].div;
-    }
-  }
   if (s_err == 0) {
-    // Hot descriptors of a request that began before the tile where their key froze
-    // (k4_place, a previous launch, recorded them and the freezing requests).
-    const uint32_t nd = s_rq[5];
-    for (uint32_t e = j * G_NT + tid; e < nd; e += gridDim.x * G_NT) {
-      const Deferred df = dfr[e];
-      const uint32_t bk = df.bucket & 0xFFFFu;
-      const HotBucket& x = hb[bk];
-      if (df.req > x.rstar) {
-        tile::emit_local_hit(out, df.idx, df.h, rules[df.rule].div - df.now_mod, rules[df.rule].shadow, routed);
-      } else {
-        tile::decide_at(df.idx, df.req, df.rule, df.h, df.now_mod, x.base, df.P, SEG_NO_FREEZE, rules, out, req_thr,
-                      routed);
-        atomicMax(hot_counter(x), (uint32_t)(x.base + df.P));
-        atomicMax(&hot_exp(hb)[bk], ((unsigned long long)df.idx << 32) | (df.bucket >> 16));
-      }
-    }
     const uint32_t nq = s_rq[0];  // ranges of group g
     for (uint32_t q = q0, it = 0; q < nq; q += RPG, ++it) {
       // Range entries are bucket << 1 | half (see k4_scan): [e0, e1) is whole buckets, or one
@@ -1583,6 +1569,35 @@ __global__ __launch_bounds__(G_NT, RL_G_OCC) void k4_group(DevBatch in,
                                     sh_w, ins, ctl, s_gen);
       }
     }
+    // The hot keys' work of this block, behind its ranges (which the kernel's length hangs on)
+    // and before it counts itself done: the last block's frozen-key pass needs all of it.
+    if (j < (uint32_t)(HOT_BUCKETS / G_NT)) {
+      // Hot keys (decided by k4_place) that no request froze: EXPIRE from the time and jitter of
+      // the last INCRBY (fixed_cache_impl.go:69-72). A key frozen in this batch gets its EXPIRE and
+      // freecache TTLs in the last block, once the deferred hot descriptors below have recorded
+      // which INCRBY of the freezing request came last.
+      const HotBucket x = hb[j * G_NT + tid];
+      if (x.slot && !(x.flags & (HB_FROZEN_PRE | HB_PS)) && x.rstar == 0xFFFFFFFFu) {
+        Slot* sl = reinterpret_cast<Slot*>(x.slot);
+        sl->exp = x.t_all + rules[x.rule].div;
+      }
+    }
+    // Hot descriptors of a request that began before the tile where their key froze
+    // (k4_place, a previous launch, recorded them and the freezing requests).
+    const uint32_t nd = s_rq[5];
+    for (uint32_t e = j * G_NT + tid; e < nd; e += gridDim.x * G_NT) {
+      const Deferred df = dfr[e];
+      const uint32_t bk = df.bucket & 0xFFFFu;
+      const HotBucket& x = hb[bk];
+      if (df.req > x.rstar) {
+        tile::emit_local_hit(out, df.idx, df.h, rules[df.rule].div - df.now_mod, rules[df.rule].shadow, routed);
+      } else {
+        tile::decide_at(df.idx, df.req, df.rule, df.h, df.now_mod, x.base, df.P, SEG_NO_FREEZE, rules, out, req_thr,
+                      routed);
+        atomicMax(hot_counter(x), (uint32_t)(x.base + df.P));
+        atomicMax(&hot_exp(hb)[bk], ((unsigned long long)df.idx << 32) | (df.bucket >> 16));
+      }
+    }
   }
   heads = tile::wave_sum(heads);
 #pragma unroll
@@ -1597,9 +1612,14 @@ __global__ __launch_bounds__(G_NT, RL_G_OCC) void k4_group(DevBatch in,
   // The last block to finish: U, hot-set candidates, next control block. Hand-off without
   // fences: every wave waits for its own stores (the sc1 ones the last block reads among
   // them), then one lane adds to the block's shard counter (blockIdx & 7); the last block of a
-  // shard adds to the global counter; the last of those is the last block.
-  if (tid == 0) st_relaxed(&wg_heads[j], s_heads);
-  if (tid < 4) st_relaxed(&wg_ins[j * 4 + tid], s_ins[2 * tid] | (s_ins[2 * tid + 1] << 16));
+  // shard adds to the global counter; the last of those is the last block. The block's key
+  // and new-slot counts go into the batch's sum counters (add_block_sums) ahead of that wait.
+  if (tid == 0) {
+    uint64_t pair[4];
+#pragma unroll
+    for (int x = 0; x < 4; ++x) pair[x] = (uint64_t)s_ins[2 * x] | ((uint64_t)s_ins[2 * x + 1] << 32);
+    add_block_sums(ctl, j, s_heads & 0xFFFFu, pair);  // (the high half counts the block's new slots)
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (tid == 0) {
@@ -1615,29 +1635,26 @@ __global__ __launch_bounds__(G_NT, RL_G_OCC) void k4_group(DevBatch in,
   __syncthreads();
   if (!s_last) return;
   STL(0);
+  // The clear of batch k+2's control block goes out first: it depends on nothing here, and
+  // its stores complete under everything below (the fence before the done word waits for them).
+  {
+    uint4* z = reinterpret_cast<uint4*>(next_ctl);
+    static_assert(sizeof(EngineCtl) % 16 == 0, "the control block is cleared in 16-B stores");
+    for (uint32_t w = tid; w < (uint32_t)(sizeof(EngineCtl) / 16); w += G_NT) z[w] = make_uint4(0, 0, 0, 0);
+  }
   // U = Σ per-block unique-key counts (this kernel and k4_scan's hot leaders); new slots per
   // region into the occupancy counts (only for a batch that was applied); the hot-set
   // candidates' prefix states. Every load the epilogue needs goes out first, in three
-  // dependent levels: (block words, candidates, occupancy) -> (candidates' prefix offsets or
+  // dependent levels: (sum counters, candidates, occupancy) -> (candidates' prefix offsets or
   // routed records) -> (prefix bytes).
-  if (tid == 0) s_heads = 0;
-  if (tid < 8) s_ins[tid] = 0;
-  constexpr int EPI = (GBLOCKS + HOT_SCAN_BLOCKS + G_NT - 1) / G_NT;
   constexpr int CPT = CAND_MAX / G_NT;  // candidate entries per thread
   static_assert(CAND_MAX % G_NT == 0, "candidates per thread");
-  const uint32_t nb = gridDim.x + n_scan_heads;
-  uint32_t hv[EPI], w[EPI][4];
+  static_assert(8 * SUM_WORDS <= G_NT && 8 * SUM_WORDS <= G_HASH, "one sum-counter word per thread");
   HotCand cc[CPT];
-  // k4_scan's hot blocks wrote their words right behind this kernel's (the engine passes
-  // scan_heads = wg_heads + gridDim.x, scan_ins = wg_ins + 4 * gridDim.x): every thread loads
-  // all of its blocks' five words at once (clamped indices), then DPP sums per wave
-#pragma unroll
-  for (int e = 0; e < EPI; ++e) {
-    const uint32_t k = min(tid + e * G_NT, nb - 1u);
-    hv[e] = ld_relaxed(&wg_heads[k]);
-#pragma unroll
-    for (int x = 0; x < 4; ++x) w[e][x] = ld_relaxed(&wg_ins[k * 4 + x]);
-  }
+  // the eight shards' sum counters: one word per thread (every block added its counts before
+  // it counted itself done, k4_scan's hot blocks a launch earlier), summed over the shards
+  // through LDS (s_cnt: no range is being grouped any more)
+  const uint32_t cw = ld_relaxed(&ctl->tile_ctr[SUM_CTR0 + ((tid / SUM_WORDS) & 7u)][tid % SUM_WORDS]);
   // candidates only for a batch whose candidates the host wants (hcand set: every 8th batch)
   const bool do_cand = hcand != nullptr;  // kernel-uniform
   if (do_cand) {
@@ -1650,26 +1667,14 @@ __global__ __launch_bounds__(G_NT, RL_G_OCC) void k4_group(DevBatch in,
   // the control block's header words for the host's copy (k4_scan's and the blocks' words are
   // final: every block's stores completed before it counted itself done)
   const uint32_t hdr = ld_relaxed(reinterpret_cast<const uint32_t*>(ctl) + (tid & 63u));
-  __syncthreads();  // s_heads / s_ins cleared
-  {
-    uint32_t u = 0, cs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (tid < 8u * SUM_WORDS) s_cnt[tid] = cw;
+  __syncthreads();
+  if (tid < (uint32_t)SUM_WORDS) {
+    uint32_t v = 0;
 #pragma unroll
-    for (int e = 0; e < EPI; ++e) {
-      if (tid + e * G_NT >= nb) continue;
-      u += hv[e] & 0xFFFFu;
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        cs[2 * x] += w[e][x] & 0xFFFFu;
-        cs[2 * x + 1] += w[e][x] >> 16;
-      }
-    }
-    u = tile::wave_sum(u);
-    if (lane == 0 && u) atomicAdd(&s_heads, u);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const uint32_t c = tile::wave_sum(cs[r]);
-      if (lane == 0 && c) atomicAdd(&s_ins[r], c);
-    }
+    for (int s = 0; s < 8; ++s) v += s_cnt[s * SUM_WORDS + tid];
+    if (tid == (uint32_t)SUM_KEYS) s_heads = v;
+    if (tid >= (uint32_t)SUM_INS && tid < (uint32_t)SUM_INS + 8u) s_ins[tid - SUM_INS] = v;  // word SUM_INS + r: region r
   }
   // candidates found by k4_group leaders carry their first descriptor: its prefix offsets (or
   // the routed record's prefix state), all loads in flight together
@@ -1707,6 +1712,29 @@ __global__ __launch_bounds__(G_NT, RL_G_OCC) void k4_group(DevBatch in,
     for (int r = 0; r < 8; ++r) n += s_ins[r];
     ctl->n_inserted = n;
   }
+  // The batch's summary straight into the host's pinned control block (header words and the
+  // candidate count): no device-to-host copy between this batch and the next one's kernels.
+  // Wave 1 writes it beside wave 0's occupancy update, from the sums in LDS; the system fence
+  // before the done word makes it visible.
+  if (hctl) {
+    constexpr uint32_t HEAD = offsetof(EngineCtl, tile_ctr) / 4;
+    static_assert(HEAD == 64 && offsetof(EngineCtl, n_segments) == 8 && offsetof(EngineCtl, n_inserted) == 12,
+                  "header words");
+    constexpr uint32_t INS0 = offsetof(EngineCtl, ins) / 4;
+    uint32_t* hw = reinterpret_cast<uint32_t*>(hctl);
+    if (tid >= 64u && tid < 64u + HEAD) {
+      const uint32_t k = tid - 64u;  // hdr was loaded at word tid & 63
+      uint32_t v = hdr;
+      if (k == 2) v = s_heads;
+      if (k == 3) {
+        v = 0;
+        for (int r = 0; r < 8; ++r) v += s_ins[r];
+      }
+      if (k >= INS0 && k < INS0 + 8) v = s_ins[k - INS0];
+      hw[k] = v;
+    }
+    if (tid == 64u + HEAD) hctl->tile_ctr[CAND_CTR][0] = nc;
+  }
   STL(1);
   if (any_cand && !in.recs) {
     u32x4 b0[CPT], b1[CPT];
@@ -1736,28 +1764,6 @@ __global__ __launch_bounds__(G_NT, RL_G_OCC) void k4_group(DevBatch in,
     }
     if (hcand) hcand[i] = c;
   }
-  // The batch's summary straight into the host's pinned control block (header words and the
-  // candidate count): no device-to-host copy between this batch and the next one's kernels.
-  __syncthreads();  // ins / n_segments / n_inserted written above by threads 0..8
-  if (hctl) {
-    constexpr uint32_t HEAD = offsetof(EngineCtl, tile_ctr) / 4;
-    static_assert(HEAD == 64 && offsetof(EngineCtl, n_segments) == 8 && offsetof(EngineCtl, n_inserted) == 12,
-                  "header words");
-    constexpr uint32_t INS0 = offsetof(EngineCtl, ins) / 4;
-    uint32_t* hw = reinterpret_cast<uint32_t*>(hctl);
-    if (tid < HEAD) {
-      uint32_t v = hdr;
-      if (tid == 2) v = s_heads;
-      if (tid == 3) {
-        v = 0;
-        for (int r = 0; r < 8; ++r) v += s_ins[r];
-      }
-      if (tid >= INS0 && tid < INS0 + 8) v = s_ins[tid - INS0];
-      hw[tid] = v;
-    }
-    if (tid == HEAD) hctl->tile_ctr[CAND_CTR][0] = nc;
-    __threadfence_system();
-  }
   // (here, where the epilogue's candidate registers are dead)
   if (tab.local_cache && s_err == 0) {
     // Hot keys a request froze in this batch (base_limiter.go:94-106): freecache TTL from the
@@ -1775,21 +1781,21 @@ __global__ __launch_bounds__(G_NT, RL_G_OCC) void k4_group(DevBatch in,
       sl->frz = t;
     }
   }
-  uint32_t* z = reinterpret_cast<uint32_t*>(next_ctl);
-  constexpr uint32_t words = sizeof(EngineCtl) / 4;
   STL(2);
-  for (uint32_t w = tid; w < words; w += G_NT) z[w] = 0;
-  STL(3);
   if (hctl) {
     // The batch is complete: the host's done word behind its pinned control block, which
     // rl_wait polls in place of a completion event. Last, after the frozen keys and the clear
     // of batch k+2's control block, which batch k+2's k4_hist (launched once the host sees this
-    // word) uses.
-    __threadfence();
+    // word) uses. One system-scope fence releases all of it, the host's header included.
+    __threadfence_system();
+    // (the compiler may drop the fence's own wait behind the L2 write-back when it can prove the
+    // wave's VMEM counter empty before the fence; a wait it cannot see keeps the done word behind it)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0)
       __hip_atomic_store(reinterpret_cast<uint32_t*>(hctl + 1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
+  STL(3);
 }
 
 }  // namespace v4
@@ -1798,7 +1804,6 @@ __global__ __launch_bounds__(G_NT, RL_G_OCC) void k4_group(DevBatch in,
 // launchers
 // ---------------------------------------------------------------------------
 uint32_t v4_tiles(uint32_t n) { return n ? (n + V4_TILE - 1) / V4_TILE : 1; }
-uint32_t v4_group_blocks(uint32_t) { return v4::GBLOCKS; }
 uint32_t v4_scan_blocks() { return v4::HOT_SCAN_BLOCKS + v4::MSD_SCAN_BLOCKS; }
 size_t v4_scratch_bytes() {
   using namespace v4;
@@ -1823,10 +1828,9 @@ void launch_v4_hist(hipStream_t st, const rl_batch& b, const DevRule* rules, uin
 }
 void launch_v4_scan(hipStream_t st, uint32_t n, const uint16_t* tstart, const unsigned long long* thsum,
                     unsigned long long* hoff, const uint32_t* fpart, const HotEntry* hot_list, HotBucket* hb,
-                    const TableDesc& tab, HotCand* cand, uint32_t* heads_out, uint32_t* ins_out, void* scratch,
-                    const uint32_t* poison, const RegionOcc* occ, EngineCtl* ctl) {
+                    const TableDesc& tab, HotCand* cand, void* scratch, const uint32_t* poison, const RegionOcc* occ, EngineCtl* ctl) {
   hipLaunchKernelGGL(v4::k4_scan, dim3(v4_scan_blocks()), dim3(v4::SCAN_NT), 0, st, tstart, thsum, v4_tiles(n), n, hoff,
-                     fpart, hot_list, hb, tab, cand, heads_out, ins_out, v4_ranges(scratch), poison, occ, ctl);
+                     fpart, hot_list, hb, tab, cand, v4_ranges(scratch), poison, occ, ctl);
 }
 void launch_v4_place(hipStream_t st, const rl_batch& b, const MRec* srec, const uint16_t* tstart,
                      void* scratch, const DevRule* rules, uint32_t n_rules, const unsigned long long* hoff,
@@ -1843,8 +1847,7 @@ void launch_v4_place(hipStream_t st, const rl_batch& b, const MRec* srec, const 
 }
 void launch_v4_group(hipStream_t st, const rl_batch& b, const DevRule* rules, uint32_t n_rules, const TableDesc& tab,
                      rl_status* out, uint32_t* req_thr, const HotBucket* hb, const Deferred* dfr, HotCand* cand,
-                     int cand_on, uint64_t seed, void* scratch, uint32_t* wg_heads, uint32_t* wg_ins,
-                     const uint32_t* scan_heads, const uint32_t* scan_ins, int routed, RegionOcc* occ, EngineCtl* ctl,
+                     int cand_on, uint64_t seed, void* scratch, int routed, RegionOcc* occ, EngineCtl* ctl,
                      EngineCtl* next_ctl, EngineCtl* hctl, HotCand* hcand, const MRec* srec,
                      const uint16_t* tstart) {
   using namespace v4;
@@ -1867,14 +1870,12 @@ void launch_v4_group(hipStream_t st, const rl_batch& b, const DevRule* rules, ui
   gs.end = reinterpret_cast<uint16_t*>(p);
   if (n_rules <= LDS_RULES)
     hipLaunchKernelGGL(k4_group<true>, dim3(GBLOCKS), dim3(G_NT), 0, st, make_dev_batch(b), rules, tab, out, req_thr,
-                       hb, dfr, cand, cand_on, seed, gs, wg_heads, wg_ins, scan_heads, scan_ins,
-                       (uint32_t)HOT_SCAN_BLOCKS, v4_ranges(scratch), routed, occ, ctl, next_ctl, hctl, hcand, srec,
-                       tstart, v4_tiles(b.n_desc), n_rules);
+                       hb, dfr, cand, cand_on, seed, gs, v4_ranges(scratch), routed, occ, ctl, next_ctl, hctl, hcand,
+                       srec, tstart, v4_tiles(b.n_desc), n_rules);
   else
     hipLaunchKernelGGL(k4_group<false>, dim3(GBLOCKS), dim3(G_NT), 0, st, make_dev_batch(b), rules, tab, out, req_thr,
-                       hb, dfr, cand, cand_on, seed, gs, wg_heads, wg_ins, scan_heads, scan_ins,
-                       (uint32_t)HOT_SCAN_BLOCKS, v4_ranges(scratch), routed, occ, ctl, next_ctl, hctl, hcand, srec,
-                       tstart, v4_tiles(b.n_desc), n_rules);
+                       hb, dfr, cand, cand_on, seed, gs, v4_ranges(scratch), routed, occ, ctl, next_ctl, hctl, hcand,
+                       srec, tstart, v4_tiles(b.n_desc), n_rules);
 }
 
 }  // namespace rlhip

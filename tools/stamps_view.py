@@ -20,8 +20,11 @@ for j in range(dd.shape[1]):
           f"  max {dd[:, j].max():7.2f}")
 L = st[4000]
 if L[0]:
-    print(f"last block: epilogue starts {(L[0] - t0) / 100:.1f} us; reductions+occ+hot finalize {(L[1] - L[0]) / 100:.2f},"
-          f" candidates {(L[2] - L[1]) / 100:.2f}, ctl clear {(L[3] - L[2]) / 100:.2f} us; ends {(L[3] - t0) / 100:.1f} us")
+    # stamps: entry; sums, occupancy and host header written; candidates and frozen keys done;
+    # behind the release fence and the done word (the next control block's clear is issued at entry)
+    print(f"last block: epilogue starts {(L[0] - t0) / 100:.1f} us; sums+occ+host header {(L[1] - L[0]) / 100:.2f},"
+          f" candidates+frozen keys {(L[2] - L[1]) / 100:.2f}, fence+done word {(L[3] - L[2]) / 100:.2f} us;"
+          f" ends {(L[3] - t0) / 100:.1f} us")
 s5 = st[2048:2048 + 96]
 s5 = s5[s5[:, 0] > 0]
 if len(s5):
