@@ -218,28 +218,34 @@ __global__ __launch_bounds__(NT) void k4_hist(DevBatch in, const DevRule* __rest
   const uint32_t tile = blockIdx.x, ntiles = gridDim.x;
   const uint32_t t0 = tile * T;
   STH(0);
+  // The descriptor loads' first level needs nothing from LDS: it is issued first, the hot table
+  // is copied and the tile's LDS words are zeroed under its latency, and the barrier that
+  // publishes them (LDS traffic only: the second level stays in flight across it) is passed
+  // under the second level's.
+  const auto staged = [&] {
 #ifndef RL_HIST_GLOBAL_HOT
-  tile::load_hot_table(hot, sh_hot);
+    tile::load_hot_table(hot, sh_hot);
 #endif
-  for (int b = tid; b < ROW / 2; b += NT) reinterpret_cast<uint32_t*>(sh_cnt)[b] = 0;
-  for (int b = tid; b < HOT_BUCKETS; b += NT) sh_hs[b] = 0;
-  if (tid < FP_PART_WORDS) sh_f[tid] = 0;
-  if (tid == 0) sh_err = 0;
-  // DoLimitResponse.ThrottleMillis starts at 0 for every request (base_limiter.go:163-165)
-  {
+    for (int b = tid; b < ROW / 2; b += NT) reinterpret_cast<uint32_t*>(sh_cnt)[b] = 0;
+    for (int b = tid; b < HOT_BUCKETS; b += NT) sh_hs[b] = 0;
+    if (tid < FP_PART_WORDS) sh_f[tid] = 0;
+    if (tid == 0) sh_err = 0;
+    // DoLimitResponse.ThrottleMillis starts at 0 for every request (base_limiter.go:163-165)
     const uint32_t per = (in.n_req + ntiles - 1) / ntiles;
     const uint32_t r0 = tile * per, r1 = min(in.n_req, r0 + per);
     if (req_thr)  // (raw replies: no ThrottleMillis slots)
       for (uint32_t q = r0 + tid; q < r1; q += NT) req_thr[q] = 0;
-  }
-  __syncthreads();
-  STH(1);
+  };
+  const auto ready = [&] {
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    STH(1);
+  };
   D3 d[R];
   uint32_t err = 0;
   if (ROUTED)
-    tile::load_routed(in, rules, n_rules, sh_hot, t0, d, err);
+    tile::load_routed(in, rules, n_rules, sh_hot, t0, d, err, staged, ready);
   else
-    tile::load_descs(in, rules, n_rules, seed, sh_hot, t0, d, err);
+    tile::load_descs(in, rules, n_rules, seed, sh_hot, t0, d, err, staged, ready);
   STH(2);
   uint32_t nil = 0;
 #pragma unroll

@@ -176,8 +176,12 @@ RL_DEV void key_of(D3& x, const FpState& s, int64_t now, const DevRule& rr, cons
   }
 }
 
+// `staged` runs once the first level is issued and `ready` once the second one is: the caller
+// fills LDS (the hot table) under the first level's latency and passes its barrier under the
+// second's; sh_hot is read only behind `ready`.
+template <class F1, class F2>
 RL_DEV void load_descs(const DevBatch& in, const DevRule* __restrict__ rules, uint32_t n_rules, uint64_t seed,
-                       const HotEntry* sh_hot, uint32_t t0, D3 (&d)[R], uint32_t& err) {
+                       const HotEntry* sh_hot, uint32_t t0, D3 (&d)[R], uint32_t& err, F1 staged, F2 ready) {
   // Every load is unconditional at a clamped index, so each of the two dependent levels (the
   // descriptor arrays; then now / hits / the rule / the prefix's first 32 bytes) issues as one
   // run of loads and waits once. A load behind a per-lane condition made the compiler wait
@@ -196,6 +200,7 @@ RL_DEV void load_descs(const DevBatch& in, const DevRule* __restrict__ rules, ui
     oa[r] = in.off[i];
     ob[r] = in.off[i + 1u];
   }
+  staged();
   HSTF(2);
   uint32_t o0[R], len[R];
   bool ok[R];
@@ -222,6 +227,7 @@ RL_DEV void load_descs(const DevBatch& in, const DevRule* __restrict__ rules, ui
     w0[r] = p[0];
     w1[r] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const uint32_t*>(p) + 4);
   }
+  ready();
   HSTF(3);
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -250,8 +256,9 @@ RL_DEV void load_descs(const DevBatch& in, const DevRule* __restrict__ rules, ui
 
 // Routed batch (owner side of the multi-GPU router): each record already carries the
 // prefix state of its key, its rule, now and hits (one 32-B load per descriptor).
+template <class F1, class F2>
 RL_DEV void load_routed(const DevBatch& in, const DevRule* __restrict__ rules, uint32_t n_rules,
-                        const HotEntry* sh_hot, uint32_t t0, D3 (&d)[R], uint32_t& err) {
+                        const HotEntry* sh_hot, uint32_t t0, D3 (&d)[R], uint32_t& err, F1 staged, F2 ready) {
   const uint32_t tid = threadIdx.x;
   RRec rc[R];
 #pragma unroll
@@ -265,6 +272,7 @@ RL_DEV void load_routed(const DevBatch& in, const DevRule* __restrict__ rules, u
       rc[r].rule = RL_NIL_RULE;
     }
   }
+  staged();
   DevRule rr[R];
   bool ok[R];
 #pragma unroll
@@ -272,6 +280,7 @@ RL_DEV void load_routed(const DevBatch& in, const DevRule* __restrict__ rules, u
     ok[r] = rrec_rule(rc[r].rule) < n_rules;
     if (ok[r]) rr[r] = rules[rrec_rule(rc[r].rule)];
   }
+  ready();
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const uint32_t i = t0 + r * NT + tid;
