@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cstdio>
 #include <cstring>
 
 namespace ratelimit {
@@ -56,6 +57,9 @@ struct PendingCall {
   size_t blob_bytes = 0;
   DoLimitResponse resp;
   std::promise<void> done;
+  // A control call (Save / Load) instead of a request: it keeps its place in the queue, and the
+  // submitter runs it with nothing in flight. Returns an error message, empty on success.
+  std::function<std::string()> ctl;
 };
 
 namespace {
@@ -195,6 +199,80 @@ HipRateLimitCache::~HipRateLimitCache() {
 void HipRateLimitCache::Flush() {
   std::unique_lock<std::mutex> g(mu_);
   idle_cv_.wait(g, [&] { return inflight_ == 0; });
+}
+
+// Save / Load: a control call through the batcher's queue, so that every engine call stays on the
+// submitter thread and the snapshot sits at one point of the serial order.
+void HipRateLimitCache::control(std::function<std::string()> f) {
+  auto call = std::make_shared<PendingCall>();
+  call->ctl = std::move(f);
+  std::future<void> fut = call->done.get_future();
+  {
+    std::lock_guard<std::mutex> g(mu_);
+    q_.push_back(call);
+    ++inflight_;
+  }
+  cv_.notify_one();
+  fut.get();  // rethrows RedisError
+}
+
+namespace {
+constexpr uint32_t kSnapChunk = 1u << 16;  // records per rl_snapshot_next / rl_restore_put
+struct File {
+  FILE* f;
+  ~File() {
+    if (f) fclose(f);
+  }
+};
+}  // namespace
+
+void HipRateLimitCache::Save(const std::string& path) {
+  control([this, path]() -> std::string {
+    File fp{fopen(path.c_str(), "wb")};
+    if (!fp.f) return "Save: cannot open " + path;
+    rl_snapshot_header h;
+    if (rl_snapshot_begin(eng_, &h)) return rl_last_error(eng_);
+    std::string msg;
+    if (fwrite(&h, sizeof h, 1, fp.f) != 1) msg = "Save: write failed: " + path;
+    std::vector<uint8_t> buf((size_t)kSnapChunk * RL_SNAP_RECORD_BYTES);
+    for (uint32_t n = 1; msg.empty() && n;) {
+      if (rl_snapshot_next(eng_, buf.data(), kSnapChunk, &n)) msg = rl_last_error(eng_);
+      else if (n && fwrite(buf.data(), RL_SNAP_RECORD_BYTES, n, fp.f) != n) msg = "Save: write failed: " + path;
+    }
+    rl_snapshot_end(eng_);
+    if (msg.empty() && fflush(fp.f)) msg = "Save: write failed: " + path;
+    return msg;
+  });
+}
+
+void HipRateLimitCache::Load(const std::string& path) {
+  control([this, path]() -> std::string {
+    File fp{fopen(path.c_str(), "rb")};
+    if (!fp.f) return "Load: cannot open " + path;
+    rl_snapshot_header h;
+    if (fread(&h, sizeof h, 1, fp.f) != 1) return "Load: " + path + " is shorter than a snapshot header";
+    if (fseek(fp.f, 0, SEEK_END)) return "Load: cannot seek " + path;
+    const long size = ftell(fp.f);
+    const uint64_t body = size < (long)sizeof h ? ~0ull : (uint64_t)size - sizeof h;
+    if (body % RL_SNAP_RECORD_BYTES || body / RL_SNAP_RECORD_BYTES != h.n_records ||
+        fseek(fp.f, (long)sizeof h, SEEK_SET))
+      return "Load: " + path + " does not hold the header and its n_records records";
+    if (rl_restore_begin(eng_, &h)) return rl_last_error(eng_);
+    std::string msg;
+    std::vector<uint8_t> buf((size_t)kSnapChunk * RL_SNAP_RECORD_BYTES);
+    for (uint64_t left = h.n_records; msg.empty() && left;) {
+      const uint32_t n = (uint32_t)std::min<uint64_t>(left, kSnapChunk);
+      if (fread(buf.data(), RL_SNAP_RECORD_BYTES, n, fp.f) != n) msg = "Load: read failed: " + path;
+      else if (rl_restore_put(eng_, buf.data(), n)) msg = rl_last_error(eng_);
+      left -= n;
+    }
+    if (!msg.empty()) {
+      rl_reset(eng_);  // closes the restore: the table is empty
+      return msg;
+    }
+    if (rl_restore_end(eng_)) return rl_last_error(eng_);
+    return "";
+  });
 }
 
 DoLimitResponse HipRateLimitCache::DoLimit(const RateLimitRequest& request,
@@ -496,6 +574,16 @@ void HipRateLimitCache::submitter() {
       first = q_.front();
       q_.pop_front();
     }
+    if (first->ctl) {
+      // every call enqueued before it is decided and answered; the engine is idle
+      for (auto& st : inflight) finish(st);
+      inflight.clear();
+      const std::string msg = first->ctl();
+      if (msg.empty()) first->done.set_value();
+      else first->done.set_exception(std::make_exception_ptr(RedisError("hip backend: " + msg)));
+      done_calls(1);
+      continue;
+    }
     Staged st;
     st.seq = staged_seq_++;
     st.compact = compactable(*first);
@@ -520,8 +608,8 @@ void HipRateLimitCache::submitter() {
         while (!q_.empty()) {
           std::shared_ptr<PendingCall> c = q_.front();
           q_.pop_front();
-          if (!fits(st, *c)) {
-            carry = std::move(c);  // starts the next batch
+          if (c->ctl || !fits(st, *c)) {
+            carry = std::move(c);  // starts the next batch (a control call: runs after this one)
             goto full;
           }
           add(st, c);

@@ -186,6 +186,21 @@ class HipRateLimitCache : public RateLimitCache {
   // waits until every enqueued call has been decided.
   void Flush() override;
 
+  // Snapshot / restore of the counter table (rl_hip.h "Snapshot / restore") to a file: the 256-B
+  // rl_snapshot_header, then n_records 32-B records, nothing else. Both go through the batcher's
+  // queue as a control call: every DoLimit enqueued before it is decided first, the engine calls
+  // run on the submitter thread with nothing in flight (all engine calls stay on one thread), and
+  // the batcher resumes with the calls enqueued behind it; DoLimit callers are held meanwhile
+  // (Save: for the export pass and the drain to the file). Load may be given a snapshot of a
+  // table of another size (HIP_TABLE_SLOTS); it needs the same HIP_HASH_SEED and REDIS_PERSECOND.
+  // The rule registry is not part of a snapshot: a record carries no rule, limits come with each
+  // request. HIP_LOCAL_CACHE=freecache: that cache lives on the host and is neither saved nor
+  // touched by Load (a restarted process starts it empty, as the reference's freecache starts).
+  // Both throw RedisError (the engine's message, or the file's); a failed Load leaves the table
+  // untouched when the header is refused, else empty.
+  void Save(const std::string& path);
+  void Load(const std::string& path);
+
   // Batcher counters (tests): batches submitted, rule-table loads, and loads made while an
   // earlier batch was still in flight (append-only rule table, rl_hip.h rl_load_rules).
   // drains: times the batches in flight were completed early so that a rule-table load or a
@@ -206,6 +221,7 @@ class HipRateLimitCache : public RateLimitCache {
  private:
   struct Staged;
   void submitter();
+  void control(std::function<std::string()> f);
   uint32_t rule_id(const RateLimitLimit& l, bool shadow);
   bool fits(const Staged& st, const PendingCall& c) const;
   bool compactable(const PendingCall& c) const;

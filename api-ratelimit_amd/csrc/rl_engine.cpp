@@ -22,6 +22,7 @@
 #include "rl_hip.h"
 #include "rl_internal.h"
 #include "rl_resolve.h"
+#include "rl_snapshot.h"
 
 namespace rlhip {
 void launch_fingerprint(hipStream_t, const rl_batch&, const DevRule*, uint32_t, uint64_t, uint64_t*, ItemRec*,
@@ -234,6 +235,53 @@ struct rl_engine {
   uint32_t* h_route = nullptr;     // pinned: [0] err, [1..16] send counts
   uint32_t* r_thr = nullptr;       // owner: ThrottleMillis per routed record
   rl_status* r_out = nullptr;      // owner: statuses per routed record
+
+  // snapshot / restore (rl_hip.h "Snapshot / restore"). The control block, the staging pair and
+  // the event are allocated at the first begin and kept; the snapshot's device copy lives from
+  // rl_snapshot_begin to rl_snapshot_end.
+  static constexpr uint32_t SNAP_STAGE_RECS = 1u << 16;  // records per staged restore chunk (2 MiB)
+  SnapCtl* d_snap_ctl = nullptr;
+  SnapCtl* h_snap_ctl = nullptr;      // pinned
+  Slot* snap_buf = nullptr;           // device copy of the live slots at rl_snapshot_begin
+  uint64_t snap_n = 0, snap_next = 0;
+  bool snap_open = false;
+  Slot* h_snap_stage = nullptr;       // pinned restore staging
+  Slot* d_snap_stage = nullptr;
+  hipEvent_t ev_snap = nullptr;       // the staged chunk's H2D copy done (h_snap_stage reusable)
+  bool restoring = false;
+  rl_snapshot_header rs_hdr{};
+  uint64_t rs_put = 0;
+  int snap_alloc() {
+    if (d_snap_ctl) return 0;
+    hipError_t he = hipMalloc(&d_snap_ctl, sizeof(SnapCtl));
+    if (he == hipSuccess) he = hipHostMalloc(&h_snap_ctl, sizeof(SnapCtl), hipHostMallocDefault);
+    if (he == hipSuccess) he = hipHostMalloc(&h_snap_stage, (size_t)SNAP_STAGE_RECS * sizeof(Slot), hipHostMallocDefault);
+    if (he == hipSuccess) he = hipMalloc(&d_snap_stage, (size_t)SNAP_STAGE_RECS * sizeof(Slot));
+    if (he == hipSuccess) he = hipEventCreateWithFlags(&ev_snap, hipEventDisableTiming);
+    if (he == hipSuccess) return 0;
+    snap_free_all();
+    return hip_fail(he, "snapshot control / staging allocation");
+  }
+  void snap_close() {
+    if (snap_buf) hipFree(snap_buf);
+    snap_buf = nullptr;
+    snap_n = snap_next = 0;
+    snap_open = false;
+  }
+  void snap_free_all() {
+    snap_close();
+    if (d_snap_ctl) hipFree(d_snap_ctl);
+    if (h_snap_ctl) hipHostFree(h_snap_ctl);
+    if (h_snap_stage) hipHostFree(h_snap_stage);
+    if (d_snap_stage) hipFree(d_snap_stage);
+    if (ev_snap) hipEventDestroy(ev_snap);
+    d_snap_ctl = nullptr;
+    h_snap_ctl = nullptr;
+    h_snap_stage = nullptr;
+    d_snap_stage = nullptr;
+    ev_snap = nullptr;
+  }
+  int clear_table();
 
   // batches in flight, oldest first
   struct Flight {
@@ -785,6 +833,7 @@ int rl_engine::finish(rl_status* out_into, uint32_t* thr_into, bool into) {
 }
 
 int rl_engine::check_batch(const rl_batch* b, bool host) {
+  if (restoring) return fail(RL_ESTATE, "submit between rl_restore_begin and rl_restore_end");
   if (b->n_desc > cfg.max_batch_desc || b->n_req > cfg.max_batch_req || (host && b->blob_bytes > cfg.max_blob_bytes))
     return fail(RL_ECAPACITY, "batch exceeds engine capacity (%u desc, %u req, %u blob bytes)", cfg.max_batch_desc,
                 cfg.max_batch_req, cfg.max_blob_bytes);
@@ -805,6 +854,7 @@ int rl_engine::check_batch(const rl_batch* b, bool host) {
 // completion point, queue the flight.
 int rl_engine::submit_common(const rl_batch& d, rl_status* out, uint32_t* thr, RReply* reply, hipEvent_t in_ev,
                              bool inputs_ready, bool host, rl_status* user_out, uint32_t* user_thr, bool raw) {
+  if (restoring) return fail(RL_ESTATE, "submit between rl_restore_begin and rl_restore_end");
   const uint32_t s = (uint32_t)(sub_seq % HSLOTS);
   h_ctl = h_ctl_s[s];
   h_cand = h_cand_s[s];
@@ -1068,6 +1118,7 @@ void rl_destroy(rl_engine* e) {
   if (!e) return;
   for (hipStream_t s : {e->stream, e->front, e->xin, e->xout})
     if (s) hipStreamSynchronize(s);
+  e->snap_free_all();
   for (auto ev : e->ev_pool) hipEventDestroy(ev);
   for (hipEvent_t ev : {e->ev_front[0], e->ev_front[1], e->ev_ready, e->ev_hot})
     if (ev) hipEventDestroy(ev);
@@ -1661,18 +1712,26 @@ int rl_route_unpack(rl_engine* e, const rl_batch* b, const uint32_t* d_perm, con
   return he == hipSuccess ? 0 : e->hip_fail(he, "rl_route_unpack");
 }
 
+// The table, hot set and candidate stash as a fresh engine has them (rl_reset, rl_restore_begin,
+// a failed rl_restore_end).
+int rl_engine::clear_table() {
+  hot.clear();
+  hot_dirty = true;
+  cand_pending = false;
+  cand_stash.clear();
+  hipError_t he = hipMemsetAsync(table, 0, table_slots * sizeof(Slot), stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(stream);
+  if (he != hipSuccess) return hip_fail(he, "rl_reset");
+  st.live_keys = 0;
+  return reset_occ();
+}
+
 int rl_reset(rl_engine* e) {
   if (!e) return RL_EINVAL;
   if (e->n_fl) return e->fail(RL_ESTATE, "rl_reset while a batch is in flight");
-  e->hot.clear();
-  e->hot_dirty = true;
-  e->cand_pending = false;
-  e->cand_stash.clear();
-  hipError_t he = hipMemsetAsync(e->table, 0, e->table_slots * sizeof(Slot), e->stream);
-  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-  if (he != hipSuccess) return e->hip_fail(he, "rl_reset");
-  e->st.live_keys = 0;
-  return e->reset_occ();
+  e->snap_close();
+  e->restoring = false;
+  return e->clear_table();
 }
 
 int rl_get_stats(rl_engine* e, rl_engine_stats* s) {
@@ -1689,6 +1748,223 @@ int rl_get_occupancy(rl_engine* e, rl_occupancy* o) {
     o->limit[r] = e->occ[r].limit;
     o->slots[r] = 1u << e->tab.region_log2[r];
   }
+  return 0;
+}
+
+// ---- Snapshot / restore -------------------------------------------------------------------
+static const uint8_t kSnapMagic[8] = {'R', 'L', 'S', 'N', 'A', 'P', '0', '1'};
+// What a snapshot header shows of hash_seed: two differently keyed mixes folded into one word,
+// enough to tell "another seed" without storing the secret.
+static uint64_t snap_seed_check(uint64_t seed) {
+  const uint64_t x = fmix64(seed ^ K0), y = fmix64(seed + K1);
+  return (x * K2) ^ rotl64(y, 31) ^ (x >> 29);
+}
+static uint32_t snap_flags(const rl_engine* e) {
+  return (e->tab.split ? RL_SNAP_SPLIT : 0u) | (e->tab.lag ? RL_SNAP_LAG : 0u) |
+         (e->tab.local_cache ? RL_SNAP_LOCAL_CACHE : 0u);
+}
+
+int rl_snapshot_begin(rl_engine* e, rl_snapshot_header* out) {
+  if (!e || !out) return RL_EINVAL;
+  if (e->n_fl) return e->fail(RL_ESTATE, "rl_snapshot_begin while a batch is in flight (call rl_wait)");
+  if (e->restoring) return e->fail(RL_ESTATE, "rl_snapshot_begin between rl_restore_begin and rl_restore_end");
+  if (e->snap_open) return e->fail(RL_ESTATE, "a snapshot is open (call rl_snapshot_end)");
+  int rc = e->snap_alloc();
+  if (rc) return rc;
+  // the mirror never under-counts (rl_common.h occ_advance): enough room for every live slot
+  uint64_t cap = 0;
+  for (int r = 0; r < 8; ++r) cap += (uint64_t)e->occ[r].live + e->occ[r].prev;
+  Slot* buf = nullptr;
+  if (cap) {
+    const hipError_t he = hipMalloc(&buf, cap * sizeof(Slot));
+    if (he != hipSuccess) {
+      (void)hipGetLastError();
+      return e->fail(RL_EHIP, "rl_snapshot_begin: no room for %llu records: %s", (unsigned long long)cap,
+                     hipGetErrorString(he));
+    }
+  }
+  SnapGens g;
+  for (int r = 0; r < 8; ++r) g.gen[r] = e->occ[r].gen;
+  hipError_t he = hipSuccess;
+  if (cap) {
+    he = hipMemsetAsync(e->d_snap_ctl, 0, sizeof(SnapCtl), e->stream);
+    if (he == hipSuccess) {
+      launch_snap_export(e->stream, e->tab, e->table_slots, g, buf, cap, e->d_snap_ctl);
+      he = hipGetLastError();
+    }
+    if (he == hipSuccess)
+      he = hipMemcpyAsync(e->h_snap_ctl, e->d_snap_ctl, sizeof(SnapCtl), hipMemcpyDeviceToHost, e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+    if (he != hipSuccess) {
+      hipFree(buf);
+      return e->hip_fail(he, "rl_snapshot_begin");
+    }
+    if (e->h_snap_ctl->err || e->h_snap_ctl->cursor > cap) {
+      hipFree(buf);
+      return e->fail(RL_EDEVICE, "rl_snapshot_begin: the table holds more live slots than its occupancy says");
+    }
+  } else {
+    memset(e->h_snap_ctl, 0, sizeof(SnapCtl));
+  }
+  rl_snapshot_header h;
+  memset(&h, 0, sizeof h);
+  memcpy(h.magic, kSnapMagic, 8);
+  h.header_bytes = RL_SNAP_HEADER_BYTES;
+  h.record_bytes = RL_SNAP_RECORD_BYTES;
+  h.flags = snap_flags(e);
+  h.seed_check = snap_seed_check(e->cfg.hash_seed);
+  for (int r = 0; r < 8; ++r) {
+    h.gen[r] = e->occ[r].gen;
+    h.live[r] = e->h_snap_ctl->cnt[2 * r][0];
+    h.prev[r] = e->h_snap_ctl->cnt[2 * r + 1][0];
+    h.src_log2[r] = e->tab.region_log2[r];
+    h.n_records += (uint64_t)h.live[r] + h.prev[r];
+  }
+  if (h.n_records != e->h_snap_ctl->cursor) {
+    hipFree(buf);
+    return e->fail(RL_EDEVICE, "rl_snapshot_begin: exported record counts disagree");
+  }
+  e->snap_buf = buf;
+  e->snap_n = h.n_records;
+  e->snap_next = 0;
+  e->snap_open = true;
+  *out = h;
+  return 0;
+}
+
+int rl_snapshot_next(rl_engine* e, void* host_buf, uint32_t cap_records, uint32_t* n) {
+  if (!e || !n) return RL_EINVAL;
+  *n = 0;
+  if (!e->snap_open) return e->fail(RL_ESTATE, "rl_snapshot_next without rl_snapshot_begin");
+  const uint64_t left = e->snap_n - e->snap_next;
+  const uint32_t take = (uint32_t)std::min<uint64_t>(left, cap_records);
+  if (!take) return 0;
+  if (!host_buf) return e->fail(RL_EINVAL, "null record buffer");
+  // the device copy only: batches submitted since rl_snapshot_begin run beside this
+  hipError_t he = hipMemcpyAsync(host_buf, e->snap_buf + e->snap_next, (size_t)take * sizeof(Slot),
+                                 hipMemcpyDeviceToHost, e->xout);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->xout);
+  if (he != hipSuccess) return e->hip_fail(he, "rl_snapshot_next");
+  e->snap_next += take;
+  *n = take;
+  return 0;
+}
+
+int rl_snapshot_end(rl_engine* e) {
+  if (!e) return RL_EINVAL;
+  e->snap_close();
+  return 0;
+}
+
+int rl_restore_begin(rl_engine* e, const rl_snapshot_header* h) {
+  if (!e || !h) return RL_EINVAL;
+  if (e->n_fl) return e->fail(RL_ESTATE, "rl_restore_begin while a batch is in flight (call rl_wait)");
+  if (e->restoring) return e->fail(RL_ESTATE, "a restore is open (call rl_restore_end)");
+  if (memcmp(h->magic, kSnapMagic, 8)) return e->fail(RL_EINVAL, "snapshot header: bad magic");
+  if (h->header_bytes != RL_SNAP_HEADER_BYTES || h->record_bytes != RL_SNAP_RECORD_BYTES)
+    return e->fail(RL_EINVAL, "snapshot header: header / record size %u / %u, expected %u / %u", h->header_bytes,
+                   h->record_bytes, RL_SNAP_HEADER_BYTES, RL_SNAP_RECORD_BYTES);
+  if (h->reserved0 || (h->flags & ~(uint32_t)(RL_SNAP_SPLIT | RL_SNAP_LAG | RL_SNAP_LOCAL_CACHE)))
+    return e->fail(RL_EINVAL, "snapshot header: unknown flags or a reserved word set");
+  for (uint32_t w : h->reserved)
+    if (w) return e->fail(RL_EINVAL, "snapshot header: a reserved word is set");
+  if (h->seed_check != snap_seed_check(e->cfg.hash_seed))
+    return e->fail(RL_EINVAL, "snapshot taken under another hash_seed");
+  const uint32_t need = RL_SNAP_SPLIT | RL_SNAP_LAG;
+  if ((h->flags & need) != (snap_flags(e) & need))
+    return e->fail(RL_EINVAL, "snapshot per_second_split / lag window setting differs from this engine's");
+  uint64_t total = 0;
+  for (int r = 0; r < 8; ++r) {
+    const bool lazy = lazy_region(e->tab.lag, (uint32_t)r);
+    if ((!h->gen[r] && (h->live[r] || h->prev[r])) || (h->prev[r] && (!lazy || h->gen[r] <= 2u)))
+      return e->fail(RL_EINVAL, "snapshot header: region %d counts without a generation to hold them", r);
+    total += (uint64_t)h->live[r] + h->prev[r];
+  }
+  if (total != h->n_records) return e->fail(RL_EINVAL, "snapshot header: n_records is not the sum of the region counts");
+  for (int r = 0; r < 8; ++r)
+    if ((uint64_t)h->live[r] + h->prev[r] > e->occ[r].limit)
+      return e->fail(RL_ENOSPC, "snapshot holds %llu records of region %d, over this engine's load limit of %u slots "
+                                "(raise log2_slots or max_load_permille)",
+                     (unsigned long long)h->live[r] + h->prev[r], r, e->occ[r].limit);
+  int rc = e->snap_alloc();
+  if (rc) return rc;
+  if ((rc = e->clear_table()) != 0) return rc;
+  hipError_t he = hipMemsetAsync(e->d_snap_ctl, 0, sizeof(SnapCtl), e->stream);
+  if (he == hipSuccess) he = hipEventRecord(e->ev_snap, e->stream);
+  if (he != hipSuccess) return e->hip_fail(he, "rl_restore_begin");
+  e->rs_hdr = *h;
+  e->rs_put = 0;
+  e->restoring = true;
+  return 0;
+}
+
+int rl_restore_put(rl_engine* e, const void* host_recs, uint32_t n) {
+  if (!e) return RL_EINVAL;
+  if (!e->restoring) return e->fail(RL_ESTATE, "rl_restore_put without rl_restore_begin");
+  if (n && !host_recs) return e->fail(RL_EINVAL, "null record buffer");
+  if (e->rs_put + n > e->rs_hdr.n_records)
+    return e->fail(RL_EINVAL, "rl_restore_put: more records than the header's %llu",
+                   (unsigned long long)e->rs_hdr.n_records);
+  SnapGens g;
+  for (int r = 0; r < 8; ++r) g.gen[r] = e->rs_hdr.gen[r];
+  const Slot* src = static_cast<const Slot*>(host_recs);
+  for (uint32_t done = 0; done < n;) {
+    const uint32_t m = std::min(n - done, rl_engine::SNAP_STAGE_RECS);
+    // the staging pair is reused once the previous chunk's copy has left it; that chunk's
+    // kernels run while this one is staged, and the device twin is ordered by the stream
+    hipError_t he = hipEventSynchronize(e->ev_snap);
+    if (he == hipSuccess) {
+      memcpy(e->h_snap_stage, src + done, (size_t)m * sizeof(Slot));
+      he = hipMemcpyAsync(e->d_snap_stage, e->h_snap_stage, (size_t)m * sizeof(Slot), hipMemcpyHostToDevice, e->stream);
+    }
+    if (he == hipSuccess) he = hipEventRecord(e->ev_snap, e->stream);
+    if (he == hipSuccess) {
+      launch_snap_import(e->stream, e->tab, e->d_snap_stage, m, g, e->d_snap_ctl);
+      he = hipGetLastError();
+    }
+    if (he != hipSuccess) return e->hip_fail(he, "rl_restore_put");
+    done += m;
+    e->rs_put += m;
+  }
+  return 0;
+}
+
+int rl_restore_end(rl_engine* e) {
+  if (!e) return RL_EINVAL;
+  if (!e->restoring) return e->fail(RL_ESTATE, "rl_restore_end without rl_restore_begin");
+  e->restoring = false;
+  hipError_t he = hipMemcpyAsync(e->h_snap_ctl, e->d_snap_ctl, sizeof(SnapCtl), hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  if (he != hipSuccess) {
+    e->hip_fail(he, "rl_restore_end");
+    const std::string msg = e->err;
+    e->clear_table();
+    e->err = msg;
+    return RL_EHIP;
+  }
+  const rl_snapshot_header& h = e->rs_hdr;
+  const uint32_t errs = e->h_snap_ctl->err;
+  const char* why = nullptr;
+  if (errs & SNAP_ERR_DUP) why = "a record's identity occurs twice";
+  else if (errs & SNAP_ERR_GEN) why = "a record's generation is neither its region's nor a lag region's previous one";
+  else if (errs & SNAP_ERR_FULL) why = "a region had no free slot left";
+  else if (e->rs_put != h.n_records) why = "fewer records than the header's n_records";
+  for (int r = 0; r < 8 && !why; ++r)
+    if (e->h_snap_ctl->cnt[2 * r][0] != h.live[r] || e->h_snap_ctl->cnt[2 * r + 1][0] != h.prev[r])
+      why = "per-region record counts differ from the header";
+  if (why) {
+    int rc = e->clear_table();  // left reset (empty)
+    if (rc) return rc;
+    return e->fail(RL_EINVAL, "rl_restore_end: %s; the engine is empty", why);
+  }
+  for (int r = 0; r < 8; ++r) {
+    e->occ[r].gen = h.gen[r];
+    e->occ[r].live = h.live[r];
+    e->occ[r].prev = h.prev[r];
+  }
+  he = hipMemcpy(e->d_occ, e->occ, sizeof e->occ, hipMemcpyHostToDevice);
+  if (he != hipSuccess) return e->hip_fail(he, "rl_restore_end: publish occupancy");
+  e->st.live_keys = e->live_total();
   return 0;
 }
 

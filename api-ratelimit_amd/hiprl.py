@@ -113,6 +113,67 @@ RAW_LOCAL_HIT, RAW_NIL = 1, 2  # rl_raw_reply.flags
 RAW_DTYPE = np.dtype([("after", "<u4"), ("flags", "<u4")])
 
 
+# ---- snapshot / restore (rl_hip.h "Snapshot / restore") ----
+SNAP_MAGIC = b"RLSNAP01"
+SNAP_HEADER_BYTES, SNAP_RECORD_BYTES = 256, 32
+SNAP_SPLIT, SNAP_LAG, SNAP_LOCAL_CACHE = 1, 2, 4  # rl_snapshot_header.flags
+# one record = one live table slot, verbatim: ctrl = window generation | tag << 32
+SNAP_DTYPE = np.dtype([("ctrl", "<u8"), ("key", "<u8"), ("count", "<u4"), ("exp", "<u4"), ("pcount", "<u4"),
+                       ("frz", "<u4")])
+SNAP_CHUNK = 1 << 16  # records per rl_snapshot_next / rl_restore_put call of save() / load()
+
+
+class RlSnapshotHeader(C.Structure):
+    _fields_ = [("magic", C.c_uint8 * 8), ("header_bytes", C.c_uint32), ("record_bytes", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved0", C.c_uint32), ("seed_check", C.c_uint64),
+                ("n_records", C.c_uint64), ("gen", C.c_uint32 * 8), ("live", C.c_uint32 * 8), ("prev", C.c_uint32 * 8),
+                ("src_log2", C.c_uint32 * 8), ("reserved", C.c_uint32 * 22)]
+
+
+def _check_snapshot_header(h: "RlSnapshotHeader"):
+    if bytes(h.magic) != SNAP_MAGIC:
+        raise ValueError("snapshot: bad magic")
+    if h.header_bytes != SNAP_HEADER_BYTES or h.record_bytes != SNAP_RECORD_BYTES:
+        raise ValueError(f"snapshot: header / record size {h.header_bytes} / {h.record_bytes}, expected "
+                         f"{SNAP_HEADER_BYTES} / {SNAP_RECORD_BYTES}")
+
+
+def _snapshot_header_from(raw: bytes) -> "RlSnapshotHeader":
+    if len(raw) != SNAP_HEADER_BYTES:
+        raise ValueError(f"snapshot: {len(raw)} header bytes, expected {SNAP_HEADER_BYTES}")
+    h = RlSnapshotHeader.from_buffer_copy(raw)
+    _check_snapshot_header(h)
+    return h
+
+
+def read_snapshot(path):
+    """A snapshot file -> (RlSnapshotHeader, records as a SNAP_DTYPE array). The file is the
+    256-B header followed by n_records 32-B records and nothing else. ValueError on a bad magic,
+    wrong sizes, or a length that is not 256 + 32 * n_records."""
+    size = os.path.getsize(path)
+    with open(path, "rb") as f:
+        h = _snapshot_header_from(f.read(SNAP_HEADER_BYTES))
+        if size != SNAP_HEADER_BYTES + SNAP_RECORD_BYTES * h.n_records:
+            raise ValueError(f"snapshot: file holds {size} bytes, its header says "
+                             f"{SNAP_HEADER_BYTES} + {SNAP_RECORD_BYTES} * {h.n_records}")
+        recs = np.fromfile(f, SNAP_DTYPE, int(h.n_records))
+    return h, recs
+
+
+def write_snapshot(path, header: "RlSnapshotHeader", records: np.ndarray):
+    """(header, SNAP_DTYPE records) -> a snapshot file. ValueError when the header is not a
+    snapshot header or its n_records is not len(records)."""
+    _check_snapshot_header(header)
+    records = np.ascontiguousarray(records)
+    if records.dtype.itemsize != SNAP_RECORD_BYTES or records.ndim != 1:
+        raise ValueError("snapshot: records must be a 1-D array of 32-byte items")
+    if header.n_records != records.shape[0]:
+        raise ValueError(f"snapshot: header says {header.n_records} records, got {records.shape[0]}")
+    with open(path, "wb") as f:
+        f.write(bytes(header))
+        records.tofile(f)
+
+
 # (name, argtypes, restype) of every symbol include/rl_hip.h declares
 class RlRouterConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_shards", C.c_uint32), ("rank", C.c_uint32), ("max_desc", C.c_uint32),
@@ -192,6 +253,12 @@ ABI = [
     ("rl_router_get_stats", [C.c_void_p, C.POINTER(RlRouterStats)], C.c_int),
     ("rl_router_last_error", [C.c_void_p], C.c_char_p),
     ("rl_router_destroy", [C.c_void_p], None),
+    ("rl_snapshot_begin", [C.c_void_p, C.POINTER(RlSnapshotHeader)], C.c_int),
+    ("rl_snapshot_next", [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)], C.c_int),
+    ("rl_snapshot_end", [C.c_void_p], C.c_int),
+    ("rl_restore_begin", [C.c_void_p, C.POINTER(RlSnapshotHeader)], C.c_int),
+    ("rl_restore_put", [C.c_void_p, C.c_void_p, C.c_uint32], C.c_int),
+    ("rl_restore_end", [C.c_void_p], C.c_int),
 ]
 
 # multi-GPU router record sizes (include/rl_hip.h RL_ROUTE_*)
@@ -636,6 +703,102 @@ class Engine:
     def reset(self):
         self._check(self.lib.rl_reset(self.h), "rl_reset")
 
+    # ---- snapshot / restore (rl_hip.h "Snapshot / restore") ----
+    def snapshot_begin(self) -> RlSnapshotHeader:
+        """rl_snapshot_begin: the table's live slots compacted into a device copy (nothing in
+        flight); the engine takes batches again once this returns."""
+        h = RlSnapshotHeader()
+        self._check(self.lib.rl_snapshot_begin(self.h, C.byref(h)), "rl_snapshot_begin")
+        return h
+
+    def snapshot_next(self, cap: int) -> np.ndarray:
+        """rl_snapshot_next: the next at most `cap` records (SNAP_DTYPE); empty when drained."""
+        buf = np.zeros(max(1, cap), SNAP_DTYPE)
+        n = C.c_uint32()
+        self._check(self.lib.rl_snapshot_next(self.h, buf.ctypes.data, cap, C.byref(n)), "rl_snapshot_next")
+        return buf[:n.value]
+
+    def snapshot_end(self):
+        self._check(self.lib.rl_snapshot_end(self.h), "rl_snapshot_end")
+
+    def snapshot_records(self, cap: int = SNAP_CHUNK):
+        """A whole snapshot in memory: (header, SNAP_DTYPE array), drained `cap` records a call."""
+        h = self.snapshot_begin()
+        try:
+            parts = []
+            while True:
+                part = self.snapshot_next(cap)
+                if not part.shape[0]:
+                    break
+                parts.append(part)
+        finally:
+            self.snapshot_end()
+        return h, (np.concatenate(parts) if parts else np.zeros(0, SNAP_DTYPE))
+
+    def restore_begin(self, header: RlSnapshotHeader):
+        self._check(self.lib.rl_restore_begin(self.h, C.byref(header)), "rl_restore_begin")
+
+    def restore_put(self, records: np.ndarray):
+        records = np.ascontiguousarray(records)
+        if records.dtype.itemsize != SNAP_RECORD_BYTES:
+            raise ValueError("snapshot records are 32-byte items")
+        self._check(self.lib.rl_restore_put(self.h, _ptr(records) or None, records.shape[0]), "rl_restore_put")
+
+    def restore_end(self):
+        self._check(self.lib.rl_restore_end(self.h), "rl_restore_end")
+
+    def restore_records(self, header: RlSnapshotHeader, records: np.ndarray, chunk: int = SNAP_CHUNK):
+        """rl_restore_begin, the records in chunks of `chunk`, rl_restore_end."""
+        self.restore_begin(header)
+        try:
+            for i in range(0, records.shape[0], chunk):
+                self.restore_put(records[i:i + chunk])
+        except Exception:
+            self.reset()  # closes the restore: the engine is left empty
+            raise
+        self.restore_end()
+
+    def save(self, path):
+        """Snapshot to a file (the 256-B header, then the records), streamed in chunks: the pause
+        is snapshot_begin; the drain runs beside whatever is submitted meanwhile."""
+        h = self.snapshot_begin()
+        try:
+            with open(path, "wb") as f:
+                f.write(bytes(h))
+                while True:
+                    part = self.snapshot_next(SNAP_CHUNK)
+                    if not part.shape[0]:
+                        break
+                    part.tofile(f)
+        finally:
+            self.snapshot_end()
+        return h
+
+    def load(self, path):
+        """Restore from a file written by save() / write_snapshot(), streamed in chunks. The
+        geometry (log2_slots) of this engine may differ from the saver's. ValueError for a
+        malformed file (nothing changed); RedisError as rl_restore_begin / _end refuse."""
+        size = os.path.getsize(path)
+        with open(path, "rb") as f:
+            h = _snapshot_header_from(f.read(SNAP_HEADER_BYTES))
+            if size != SNAP_HEADER_BYTES + SNAP_RECORD_BYTES * h.n_records:
+                raise ValueError(f"snapshot: file holds {size} bytes, its header says "
+                                 f"{SNAP_HEADER_BYTES} + {SNAP_RECORD_BYTES} * {h.n_records}")
+            self.restore_begin(h)
+            try:
+                left = int(h.n_records)
+                while left:
+                    part = np.fromfile(f, SNAP_DTYPE, min(left, SNAP_CHUNK))
+                    if not part.shape[0]:
+                        break  # rl_restore_end reports the missing records
+                    self.restore_put(part)
+                    left -= part.shape[0]
+            except Exception:
+                self.reset()
+                raise
+            self.restore_end()
+        return h
+
     def stats(self) -> dict:
         s = RlEngineStats()
         self._check(self.lib.rl_get_stats(self.h, C.byref(s)), "rl_get_stats")
@@ -972,6 +1135,15 @@ class HipRateLimitCache:
 
     def Flush(self):
         pass
+
+    def save(self, path):
+        """Snapshot the counters to a file (Engine.save). The rule registry is not part of it: a
+        record carries no rule, and the limits come with each request."""
+        return self.engine.save(path)
+
+    def load(self, path):
+        """Restore the counters from a snapshot file (Engine.load)."""
+        return self.engine.load(path)
 
     def do_limit_batch(self, calls) -> list:
         reqs = []

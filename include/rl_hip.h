@@ -542,6 +542,78 @@ int rl_kernel_times(rl_engine* e, const char** names, double* total_ms, uint64_t
 int rl_last_batch_info(rl_engine* e, uint64_t* unique_keys, uint64_t* n_desc, uint64_t* n_req,
                        uint64_t* blob_bytes);
 
+/* ---- Snapshot / restore -------------------------------------------------
+ * The counter table is the whole state of the backend (the hot set is a cache and is learned
+ * again). A snapshot is a fixed header and one 32-B record per live table slot, verbatim: the
+ * claim word (window generation | tag << 32), the sort key (region | 58 fingerprint bits), both
+ * counters, the main store's expiry second and the local-cache deadline. A slot's place is the
+ * top bits of its key, so the records restore into a table of any size: log2_slots may differ in
+ * every region between the engine that saved and the one that loads. No counterpart in the
+ * reference, whose counters live in Redis and survive a restart of the service there.
+ *
+ * What is live: a slot of region r whose generation g is not 0 and equals the region's newest
+ * generation (rl_occupancy.gen[r]) or, in a lag region (RL_CFG_LAG_WINDOW, the two SECOND-home
+ * regions), g + 2 == that generation — exactly the slots a request at the table's newest time
+ * can still find. Record order is unspecified; the set is exact.
+ *
+ * Saving: rl_snapshot_begin (nothing in flight, else RL_ESTATE) compacts the live slots into a
+ * device buffer sized from the occupancy mirror (one streaming pass over the table, then a
+ * stream synchronise: that pass is the whole pause) and fills *out; live[] / prev[] are the
+ * counts the pass exported. If the buffer cannot be allocated: RL_EHIP, nothing changed. From
+ * then on the engine takes batches again: rl_snapshot_next copies the next at most cap_records
+ * records of that device copy to host_buf (*n = 0: drained) and never reads the table, so the
+ * records are the state at begin whatever was submitted since. rl_snapshot_end frees the copy
+ * (legal at any point, also with none open). One snapshot at a time per engine.
+ *
+ * Loading: rl_restore_begin validates before anything changes — magic, header_bytes,
+ * record_bytes, reserved words, seed_check against this engine's hash_seed, RL_SNAP_SPLIT and
+ * RL_SNAP_LAG against its settings (RL_SNAP_LOCAL_CACHE may differ: the local-cache deadline of
+ * a record is simply unused with the cache off), n_records against the per-region counts: RL_EINVAL
+ * otherwise; live[r] + prev[r] over the region's load limit: RL_ENOSPC; either way the engine is
+ * untouched. Needs nothing in flight (RL_ESTATE). Then the table, hot set and candidate stash
+ * are cleared as rl_reset clears them, and every submit returns RL_ESTATE until rl_restore_end.
+ * rl_restore_put imports n records from host memory (any chunking; staged through bounded pinned
+ * memory); a call that would pass the header's n_records imports nothing and returns RL_EINVAL
+ * (the restore stays open: rl_restore_end or rl_reset closes it). rl_restore_end checks what arrived against the header: on success the occupancy
+ * becomes the header's {gen, live, prev} (the load limits stay this engine's) and
+ * rl_engine_stats.live_keys follows; inserted_keys is cumulative and is not restored. A record
+ * whose identity occurs twice, a generation that is neither gen[r] nor a lag region's gen[r] - 2,
+ * or counts that differ from the header: RL_EINVAL, and the engine is left reset (empty).
+ * rl_reset and rl_destroy close an open snapshot or restore.
+ *
+ * A routed deployment saves and loads per rank: a record does not carry what the owner hash
+ * needs, so a restore needs the same n_shards and hash_seed; and such an engine must have
+ * RL_CFG_LAG_WINDOW from rl_create, or its router created first, before it is restored. */
+#define RL_SNAP_RECORD_BYTES 32u
+#define RL_SNAP_HEADER_BYTES 256u
+enum {
+  RL_SNAP_SPLIT = 1u,       /* rl_config.per_second_split */
+  RL_SNAP_LAG = 2u,         /* RL_CFG_LAG_WINDOW */
+  RL_SNAP_LOCAL_CACHE = 4u  /* rl_config.local_cache (informational) */
+};
+typedef struct rl_snapshot_header { /* 256 B, little-endian, reserved words 0 */
+  uint8_t magic[8];        /* "RLSNAP01" */
+  uint32_t header_bytes;   /* RL_SNAP_HEADER_BYTES */
+  uint32_t record_bytes;   /* RL_SNAP_RECORD_BYTES */
+  uint32_t flags;          /* RL_SNAP_* */
+  uint32_t reserved0;
+  uint64_t seed_check;     /* a mix of hash_seed, never the seed itself (it is a secret) */
+  uint64_t n_records;      /* = sum of live[] and prev[] */
+  uint32_t gen[8];         /* per region: newest window generation (0 = unused) */
+  uint32_t live[8];        /* records of that generation */
+  uint32_t prev[8];        /* records of generation gen - 2 (lag regions; else 0) */
+  uint32_t src_log2[8];    /* log2 of the region sizes of the engine that saved (informational) */
+  uint32_t reserved[22];
+} rl_snapshot_header;
+
+int rl_snapshot_begin(rl_engine* e, rl_snapshot_header* out);
+int rl_snapshot_next(rl_engine* e, void* host_buf, uint32_t cap_records, uint32_t* n);
+int rl_snapshot_end(rl_engine* e);
+
+int rl_restore_begin(rl_engine* e, const rl_snapshot_header* hdr);
+int rl_restore_put(rl_engine* e, const void* host_recs, uint32_t n);
+int rl_restore_end(rl_engine* e);
+
 /* ---- Descriptor-tree resolution (GetLimit) ------------------------
  * Replaces rateLimitConfigImpl.GetLimit (src/config/config_impl.go:274-323) per descriptor,
  * batched on the device: it yields the rule id each descriptor of an rl_batch carries.
