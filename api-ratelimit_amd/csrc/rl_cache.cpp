@@ -275,6 +275,78 @@ void HipRateLimitCache::Load(const std::string& path) {
   });
 }
 
+// Peek / Forget: the request's descriptors as one rl_batch of one request, built and handed to
+// rl_peek / rl_forget by the submitter thread (a control call), at the time it reads there.
+std::vector<HipRateLimitCache::PeekStatus> HipRateLimitCache::peek_call(
+    const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits, bool forget) {
+  if (request.Descriptors.size() != limits.size())
+    throw std::logic_error("assert: len(request.Descriptors) == len(limits)");
+  const size_t n = limits.size();
+  // GenerateCacheKey prefixes (cache_key.go:57-65), on the caller's thread
+  std::vector<uint8_t> blob;
+  std::vector<uint32_t> off(n + 1, 0);
+  for (size_t i = 0; i < n; ++i) {
+    if (limits[i]) {
+      std::string p = request.Domain;
+      p += '_';
+      for (const auto& e : request.Descriptors[i].Entries) {
+        p += e.Key;
+        p += '_';
+        p += e.Value;
+        p += '_';
+      }
+      blob.insert(blob.end(), p.begin(), p.end());
+    }
+    off[i + 1] = (uint32_t)blob.size();
+  }
+  std::vector<PeekStatus> result(n);
+  control([&]() -> std::string {
+    if (trace_) trace_(&request, staged_seq_, kTraceControl);
+    if (!n) return "";
+    std::vector<uint32_t> rule(n), req_of(n, 0u);
+    for (size_t i = 0; i < n; ++i)
+      rule[i] = limits[i] ? rule_id(limits[i]->Limit, limits[i]->ShadowMode) : RL_NIL_RULE;
+    if (rules_dirty_) {  // nothing is in flight: any table may be loaded
+      if (rl_load_rules(eng_, rules_.data(), (uint32_t)rules_.size())) return rl_last_error(eng_);
+      rules_dirty_ = false;
+      n_loads_ += 1;
+    }
+    const int64_t now = ts_->UnixNow();
+    rl_batch b;
+    memset(&b, 0, sizeof b);
+    b.n_desc = (uint32_t)n;
+    b.n_req = 1;
+    b.blob_bytes = (uint32_t)blob.size();
+    b.prefix_blob = blob.data();
+    b.prefix_off = off.data();
+    b.rule_id = rule.data();
+    b.req_of = req_of.data();
+    b.now = &now;
+    std::vector<rl_peek_reply> rep(n);
+    if (forget ? rl_forget(eng_, &b, rep.data()) : rl_peek(eng_, &b, rep.data())) return rl_last_error(eng_);
+    for (size_t i = 0; i < n; ++i) {
+      PeekStatus& s = result[i];
+      s.Found = (rep[i].flags & RL_PEEK_FOUND) != 0;
+      s.LocalCached = (rep[i].flags & RL_PEEK_LOCAL_CACHED) != 0;
+      s.Count = rep[i].count;
+      s.TtlSeconds = rep[i].ttl_s;
+      s.CachedSeconds = rep[i].cached_s;
+    }
+    return "";
+  });
+  return result;
+}
+
+std::vector<HipRateLimitCache::PeekStatus> HipRateLimitCache::Peek(
+    const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits) {
+  return peek_call(request, limits, false);
+}
+
+std::vector<HipRateLimitCache::PeekStatus> HipRateLimitCache::Forget(
+    const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits) {
+  return peek_call(request, limits, true);
+}
+
 DoLimitResponse HipRateLimitCache::DoLimit(const RateLimitRequest& request,
                                            const std::vector<std::shared_ptr<RateLimit>>& limits) {
   auto call = make_call(request, limits, *ts_);

@@ -145,7 +145,9 @@ struct PendingCall;
 
 // Test hook of both batchers: every call's place in the serial order as it is put in a batch —
 // (the batch's / step's sequence number, the call's request position in it). The serial order
-// of one engine is (batch, position); of a routed deployment (step, rank, position).
+// of one engine is (batch, position); of a routed deployment (step, rank, position). A Peek /
+// Forget of HipRateLimitCache is reported as (the next batch to be gathered, kTraceControl): it
+// comes after every call of the batches before that one and before every call of it.
 using TraceFn = std::function<void(const RateLimitRequest* request, uint64_t seq, uint32_t pos)>;
 
 // HIP_* settings (BACKEND_TYPE=hip)
@@ -201,6 +203,29 @@ class HipRateLimitCache : public RateLimitCache {
   void Save(const std::string& path);
   void Load(const std::string& path);
 
+  // Peek / Forget (rl_hip.h "Peek / forget"): what an operator asks Redis with GET / TTL and DEL,
+  // per descriptor of a request as DoLimit would key it (limits[i] == nullptr: no lookup, a zero
+  // status). Peek spends nothing (no hit, no stat, no jitter draw); Forget clears the descriptor's
+  // counter on its store and the string's device local-cache entry, so the next DoLimit counts
+  // from 0, and returns what Peek would have returned just before. Both are control calls like
+  // Save / Load: every DoLimit enqueued before them is decided first, the engine call runs on
+  // the submitter thread with nothing in flight, and the time is ts_->UnixNow() taken there, so
+  // their place in the serial order is well defined (the trace hook reports it: the sequence
+  // number of the first batch gathered after the call, position kTraceControl). A new
+  // (RequestsPerUnit, unit) is registered as DoLimit registers it. Errors throw RedisError.
+  // HIP_LOCAL_CACHE=freecache: that cache lives on the host and is neither reported (LocalCached
+  // is false) nor cleared; its entries expire after at most one divider.
+  // Out of scope: HipRoutedRateLimitCache (each rank's engine answers only for the keys it owns,
+  // the others read as absent: a routed peek is a later change) and a compact wire form.
+  struct PeekStatus {
+    bool Found = false, LocalCached = false;
+    uint32_t Count = 0, TtlSeconds = 0, CachedSeconds = 0;
+  };
+  static constexpr uint32_t kTraceControl = 0xFFFFFFFFu;
+  std::vector<PeekStatus> Peek(const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits);
+  std::vector<PeekStatus> Forget(const RateLimitRequest& request,
+                                 const std::vector<std::shared_ptr<RateLimit>>& limits);
+
   // Batcher counters (tests): batches submitted, rule-table loads, and loads made while an
   // earlier batch was still in flight (append-only rule table, rl_hip.h rl_load_rules).
   // drains: times the batches in flight were completed early so that a rule-table load or a
@@ -222,6 +247,8 @@ class HipRateLimitCache : public RateLimitCache {
   struct Staged;
   void submitter();
   void control(std::function<std::string()> f);
+  std::vector<PeekStatus> peek_call(const RateLimitRequest& request,
+                                    const std::vector<std::shared_ptr<RateLimit>>& limits, bool forget);
   uint32_t rule_id(const RateLimitLimit& l, bool shadow);
   bool fits(const Staged& st, const PendingCall& c) const;
   bool compactable(const PendingCall& c) const;

@@ -123,6 +123,47 @@ RL_DEV bool table_claim(const TableDesc& tab, uint64_t key, uint64_t fp_lo, uint
   return table_claim_pre(tab, key, fp_lo, G, load_slot(slot_first(tab, key)), slot_out, existed_out, st_out);
 }
 
+// Read-only lookup of (key, fp_lo) for window generation G (rl_peek / rl_forget), with the first
+// probe slot already read (pre): the slot and its state, or false. No CAS and no store. The walk
+// ends at the first slot that is free for G (slot_free_for) and is bounded by the region size.
+// Why stopping there is right, with nothing in flight (no claim races the walk): the key's
+// leader claimed the first slot of this chain that was free for G when it walked it, so every
+// slot before the key's was then held by a generation that is not free for G. A slot's
+// generation only ever grows — a claim replaces g by a G' for which g was free, i.e. g < G'
+// (g + 2 < G' in a lag region) — so a slot that was not free for G never becomes free for G
+// again: claims of generation G are permanent while G lasts, and a newer generation leaves
+// behind a generation above G wherever it claims. The walk therefore cannot stop before the
+// key's slot while that slot still holds the key. If a newer generation took the
+// key's slot, the string's window has expired; the walk passes over it (not free for G) and ends
+// at a free slot or after the whole region: absent, which is also what a submit would see (it
+// would claim a fresh slot with zero state).
+RL_DEV bool table_find(const TableDesc& tab, uint64_t key, uint64_t fp_lo, uint32_t G, const SlotView pre,
+                       Slot*& slot_out, KeyState& st_out) {
+  uint64_t rb;
+  uint32_t lg;
+  region_geom(tab, key_region(key), rb, lg);
+  const uint64_t mask = (1ull << lg) - 1ull;
+  Slot* rbase = tab.slots + rb;
+  uint64_t pos = (key << 3) >> (64 - lg);
+  const uint32_t tag = (uint32_t)fp_lo;
+  const bool lazy = lazy_region(tab.lag, key_region(key));
+  slot_out = nullptr;
+  st_out = KeyState{0, 0, 0, 0};
+  SlotView cur = pre;
+  for (uint64_t probe = 0; probe <= mask; ++probe) {
+    const uint32_t g = (uint32_t)cur.ctrl;
+    if (g == G && (uint32_t)(cur.ctrl >> 32) == tag && cur.key == key) {
+      slot_out = rbase + (pos & mask);
+      st_out = cur.st;
+      return true;
+    }
+    if (slot_free_for(g, G, lazy)) return false;
+    ++pos;
+    cur = load_slot(rbase + (pos & mask));
+  }
+  return false;
+}
+
 // Fast-path state of a key all of whose descriptors in the batch have one unit (one store),
 // touched inside its window [ws, ws + div): the counter before the batch and whether the
 // local cache holds the key for the whole batch. False when an expiry can fall among the

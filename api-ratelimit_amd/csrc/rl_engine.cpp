@@ -75,6 +75,8 @@ void launch_v4_group(hipStream_t st, const rl_batch& b, const DevRule* rules, ui
                      int cand_on, uint64_t seed, void* scratch, int routed, RegionOcc* occ, EngineCtl* ctl,
                      EngineCtl* next_ctl, EngineCtl* hctl, HotCand* hcand, const MRec* srec,
                      const uint16_t* tstart);
+void launch_peek(hipStream_t, const rl_batch&, const DevRule*, uint32_t, uint64_t, const TableDesc&, rl_peek_reply*,
+                 bool forget);
 }  // namespace rlhip
 
 using namespace rlhip;
@@ -1965,6 +1967,106 @@ int rl_restore_end(rl_engine* e) {
   he = hipMemcpy(e->d_occ, e->occ, sizeof e->occ, hipMemcpyHostToDevice);
   if (he != hipSuccess) return e->hip_fail(he, "rl_restore_end: publish occupancy");
   e->st.live_keys = e->live_total();
+  return 0;
+}
+
+// ---- Peek / forget ------------------------------------------------------------------------
+// What every form checks first: the call's place among the batches, the arguments' shape and
+// the engine's capacities (blob_bytes only where the engine stages the blob).
+static int peek_enter(rl_engine* e, const rl_batch* b, const char* what, bool host) {
+  if (e->n_fl) return e->fail(RL_ESTATE, "%s while a batch is in flight (call rl_wait)", what);
+  if (e->restoring) return e->fail(RL_ESTATE, "%s between rl_restore_begin and rl_restore_end", what);
+  if (b->n_desc > e->cfg.max_batch_desc || b->n_req > e->cfg.max_batch_req ||
+      (host && b->blob_bytes > e->cfg.max_blob_bytes))
+    return e->fail(RL_ECAPACITY, "%s: batch exceeds engine capacity (%u desc, %u req, %u blob bytes)", what,
+                   e->cfg.max_batch_desc, e->cfg.max_batch_req, e->cfg.max_blob_bytes);
+  if (b->reserved) return e->fail(RL_EINVAL, "rl_batch.reserved must be 0");
+  if (b->n_desc && (!b->prefix_off || !b->rule_id || !b->req_of)) return e->fail(RL_EINVAL, "null descriptor array");
+  if (b->n_req && !b->now) return e->fail(RL_EINVAL, "null request times");
+  if (b->n_desc && !b->n_req) return e->fail(RL_EINVAL, "descriptors without requests");
+  if (b->n_desc && !b->prefix_blob && (!host || b->blob_bytes))
+    return e->fail(RL_EINVAL, "null prefix_blob (a device blob must be readable even when empty)");
+  if (!e->d_rules) return rl_load_rules(e, nullptr, 0);
+  return 0;
+}
+
+// rl_peek / rl_forget: validate on the host, stage, look up (and clear), copy the replies out.
+static int peek_host(rl_engine* e, const rl_batch* b, rl_peek_reply* out, bool forget) {
+  const char* what = forget ? "rl_forget" : "rl_peek";
+  int rc = peek_enter(e, b, what, true);
+  if (rc) return rc;
+  if (b->n_desc && !forget && !out) return e->fail(RL_EINVAL, "rl_peek: null reply array");
+  for (uint32_t r = 0; r < b->n_req; ++r)
+    if (b->now[r] < 0 || b->now[r] > MAX_NOW)
+      return e->fail(RL_EINVAL, "%s: request %u: time %lld outside [0, 0xFFFD0000]", what, r, (long long)b->now[r]);
+  for (uint32_t i = 0; i < b->n_desc; ++i) {
+    if (b->prefix_off[i] > b->prefix_off[i + 1] || b->prefix_off[i + 1] > b->blob_bytes)
+      return e->fail(RL_EINVAL, "%s: descriptor %u: prefix offsets out of order or past blob_bytes", what, i);
+    if (b->req_of[i] >= b->n_req || (i && b->req_of[i] < b->req_of[i - 1]))
+      return e->fail(RL_EINVAL, "%s: descriptor %u: request index %u decreases or is not below n_req", what, i,
+                     b->req_of[i]);
+    if (b->rule_id[i] != RL_NIL_RULE && b->rule_id[i] >= e->n_rules)
+      return e->fail(RL_EINVAL, "%s: descriptor %u: unknown rule id %u", what, i, b->rule_id[i]);
+  }
+  if (!b->n_desc) return 0;
+  // Nothing is in flight, so every host staging slot is idle. The slot after the next submit's is
+  // used: rl_host_acquire may have handed that one out already, and only a slot's pinned outputs
+  // (never touched here) back the views of rl_wait_view. The device outputs of the slot hold the
+  // replies (16 B against the 20 B of a status).
+  rl_engine::Stage& g = e->stage[(e->sub_seq + 1) % HSLOTS];
+  uint8_t* h = g.h_in;
+  struct Arr { const void* src; size_t o, n; } arrs[] = {
+      {b->prefix_blob, 0, b->blob_bytes}, {b->prefix_off, e->o_off, ((size_t)b->n_desc + 1) * 4},
+      {b->rule_id, e->o_rule, (size_t)b->n_desc * 4}, {b->req_of, e->o_req, (size_t)b->n_desc * 4},
+      {b->now, e->o_now, (size_t)b->n_req * 8}};
+  for (auto& a : arrs)
+    if (a.n) memcpy(h + a.o, a.src, a.n);
+  memset(h + b->blob_bytes, 0, RL_BLOB_SLACK);  // the device reads prefixes in 16-B words
+  arrs[0].n += RL_BLOB_SLACK;
+  hipError_t he = hipSuccess;
+  for (auto& a : arrs)
+    if (he == hipSuccess) he = hipMemcpyAsync(g.d_in + a.o, h + a.o, a.n, hipMemcpyHostToDevice, e->stream);
+  if (he != hipSuccess) return e->hip_fail(he, "peek staging");
+  rl_batch d = *b;
+  d.prefix_blob = g.d_in;
+  d.prefix_off = reinterpret_cast<const uint32_t*>(g.d_in + e->o_off);
+  d.rule_id = reinterpret_cast<const uint32_t*>(g.d_in + e->o_rule);
+  d.req_of = reinterpret_cast<const uint32_t*>(g.d_in + e->o_req);
+  d.now = reinterpret_cast<const int64_t*>(g.d_in + e->o_now);
+  d.hits_addend = nullptr;
+  d.ttl_jitter = nullptr;
+  rl_peek_reply* d_rep = reinterpret_cast<rl_peek_reply*>(g.d_out);
+  static_assert(sizeof(rl_peek_reply) <= sizeof(rl_status), "the replies fit the slot's status array");
+  // the replies first (the state before the call, for every duplicate), then the clears
+  if (out) launch_peek(e->stream, d, e->d_rules, e->n_rules, e->cfg.hash_seed, e->tab, d_rep, false);
+  if (forget) launch_peek(e->stream, d, e->d_rules, e->n_rules, e->cfg.hash_seed, e->tab, d_rep, true);
+  he = hipGetLastError();
+  if (he == hipSuccess && out)
+    he = hipMemcpyAsync(out, d_rep, (size_t)b->n_desc * sizeof(rl_peek_reply), hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  if (he != hipSuccess) return e->hip_fail(he, what);
+  return 0;
+}
+
+int rl_peek(rl_engine* e, const rl_batch* b, rl_peek_reply* out) {
+  if (!e || !b) return RL_EINVAL;
+  return peek_host(e, b, out, false);
+}
+
+int rl_forget(rl_engine* e, const rl_batch* b, rl_peek_reply* out_or_null) {
+  if (!e || !b) return RL_EINVAL;
+  return peek_host(e, b, out_or_null, true);
+}
+
+int rl_peek_device(rl_engine* e, const rl_batch* b, rl_peek_reply* d_out) {
+  if (!e || !b) return RL_EINVAL;
+  int rc = peek_enter(e, b, "rl_peek_device", false);
+  if (rc) return rc;
+  if (!b->n_desc) return 0;
+  if (!d_out) return e->fail(RL_EINVAL, "rl_peek_device: null reply array");
+  launch_peek(e->stream, *b, e->d_rules, e->n_rules, e->cfg.hash_seed, e->tab, d_out, false);
+  const hipError_t he = hipGetLastError();
+  if (he != hipSuccess) return e->hip_fail(he, "rl_peek_device");
   return 0;
 }
 

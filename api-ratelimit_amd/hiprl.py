@@ -113,6 +113,11 @@ RAW_LOCAL_HIT, RAW_NIL = 1, 2  # rl_raw_reply.flags
 RAW_DTYPE = np.dtype([("after", "<u4"), ("flags", "<u4")])
 
 
+# ---- peek / forget (rl_hip.h "Peek / forget") ----
+PEEK_FOUND, PEEK_LOCAL_CACHED, PEEK_NIL, PEEK_PER_SECOND, PEEK_BAD = 1, 2, 4, 8, 16  # rl_peek_reply.flags
+PEEK_DTYPE = np.dtype([("count", "<u4"), ("ttl_s", "<u4"), ("cached_s", "<u4"), ("flags", "<u4")])
+
+
 # ---- snapshot / restore (rl_hip.h "Snapshot / restore") ----
 SNAP_MAGIC = b"RLSNAP01"
 SNAP_HEADER_BYTES, SNAP_RECORD_BYTES = 256, 32
@@ -259,6 +264,9 @@ ABI = [
     ("rl_restore_begin", [C.c_void_p, C.POINTER(RlSnapshotHeader)], C.c_int),
     ("rl_restore_put", [C.c_void_p, C.c_void_p, C.c_uint32], C.c_int),
     ("rl_restore_end", [C.c_void_p], C.c_int),
+    ("rl_peek", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
+    ("rl_peek_device", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
+    ("rl_forget", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
 ]
 
 # multi-GPU router record sizes (include/rl_hip.h RL_ROUTE_*)
@@ -702,6 +710,33 @@ class Engine:
 
     def reset(self):
         self._check(self.lib.rl_reset(self.h), "rl_reset")
+
+    # ---- peek / forget (rl_hip.h "Peek / forget") ----
+    def peek(self, b: Batch) -> np.ndarray:
+        """rl_peek of a host batch (hits and jitter ignored): per descriptor the counter, TTL and
+        local-cache state a submit of it would read before its INCRBY (PEEK_DTYPE). Writes
+        nothing; needs nothing in flight."""
+        out = np.zeros(b.n_desc, PEEK_DTYPE)
+        s = _batch_struct(b)
+        self._check(self.lib.rl_peek(self.h, C.byref(s), _ptr(out) or None), "rl_peek")
+        return out
+
+    def forget(self, b: Batch) -> np.ndarray:
+        """rl_forget of a host batch: DEL of each descriptor's counter on its store and of the
+        string's local-cache entry; returns the replies as read before the clear (PEEK_DTYPE)."""
+        out = np.zeros(b.n_desc, PEEK_DTYPE)
+        s = _batch_struct(b)
+        self._check(self.lib.rl_forget(self.h, C.byref(s), _ptr(out) or None), "rl_forget")
+        return out
+
+    def peek_device(self, n_desc: int, n_req: int, blob_bytes: int, ptrs, out_ptr: int):
+        """rl_peek_device: an rl_batch of device pointers (ptrs = blob, off, rule, req_of, now, hits
+        or 0) -> n_desc rl_peek_reply in device memory at out_ptr, asynchronous on the engine
+        stream. A malformed descriptor gets PEEK_BAD."""
+        s = RlBatch()
+        s.n_desc, s.n_req, s.blob_bytes, s.reserved = n_desc, n_req, blob_bytes, 0
+        _set_ptrs(s, ptrs)
+        self._check(self.lib.rl_peek_device(self.h, C.byref(s), out_ptr), "rl_peek_device")
 
     # ---- snapshot / restore (rl_hip.h "Snapshot / restore") ----
     def snapshot_begin(self) -> RlSnapshotHeader:

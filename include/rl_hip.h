@@ -614,6 +614,62 @@ int rl_restore_begin(rl_engine* e, const rl_snapshot_header* hdr);
 int rl_restore_put(rl_engine* e, const void* host_recs, uint32_t n);
 int rl_restore_end(rl_engine* e);
 
+/* ---- Peek / forget: read and clear counters by key -----------------------
+ * What an operator does to the Redis backend with GET / TTL domain_key_value_<window> and DEL,
+ * and what freecache's Get answers for the local over-limit cache, by key and on the device. The
+ * batch is an ordinary rl_batch, the one a caller would submit: hits_addend and ttl_jitter are
+ * ignored and may be NULL; req_of and now give each descriptor its time.
+ *
+ * rl_peek: descriptor i reads exactly the state an rl_submit of the same batch would read for it
+ * before its INCRBY, and writes nothing. The key string is prefix || decimal((now/div)*div) under
+ * the rule's unit; its table region and window generation follow from that window start, its
+ * store (main or per-second) from the rule's unit and rl_config.per_second_split.
+ *   RL_PEEK_FOUND         main store: the string's slot exists for that generation and now < its
+ *                         expiry; per-second store: the slot exists and its counter is not 0
+ *   RL_PEEK_LOCAL_CACHED  rl_config.local_cache is on and now < the string's local-cache deadline
+ *   RL_PEEK_NIL           the rule is RL_NIL_RULE: nothing is looked up
+ *   RL_PEEK_PER_SECOND    the descriptor's store is the per-second one
+ *   RL_PEEK_BAD           rl_peek_device only: a malformed descriptor (below); every other word 0
+ * rl_forget: Redis DEL on the descriptor's store (main: counter and expiry; per-second: counter)
+ * plus dropping the string's local-cache entry. The table slot stays claimed for its window
+ * generation (open addressing without tombstones), so occupancy, live_keys and inserted_keys do
+ * not change and the next INCRBY of the string starts from 0, exactly as after DEL. A string
+ * that is absent is left alone: nothing is claimed. out (may be NULL) receives each descriptor's
+ * reply as rl_peek would have given it before the call, duplicates within the call included. The
+ * hot set and the candidate stash hold prefixes, not counters, and are not touched.
+ *
+ * rl_peek / rl_forget take host memory and are synchronous (staged through a free host staging
+ * slot, never the one rl_host_acquire handed out; results rl_wait_view handed out stay valid).
+ * Before anything is staged they refuse: an unknown rule id, a time outside [0, 0xFFFD0000], a
+ * decreasing req_of or a request index >= n_req, prefix offsets out of order or past blob_bytes
+ * (RL_EINVAL); n_desc, n_req or blob_bytes over the engine's capacities (RL_ECAPACITY).
+ * rl_peek_device takes device memory (the blob readable for RL_BLOB_SLACK bytes past blob_bytes,
+ * as for rl_submit_device), runs on the engine stream and returns at once; it cannot see such an
+ * error, so a malformed descriptor gets flags = RL_PEEK_BAD and zeros, and the others are answered.
+ * All three return RL_ESTATE while a batch is in flight (the rl_get_occupancy rule: a batcher
+ * calls them between batches) and between rl_restore_begin and rl_restore_end. An open snapshot
+ * does not block them: the snapshot is the state at its begin.
+ *
+ * Out of scope: a routed deployment (each rank's engine answers for the keys it owns; the others
+ * read as absent there), and a compact wire form. */
+enum {
+  RL_PEEK_FOUND = 1u,
+  RL_PEEK_LOCAL_CACHED = 2u,
+  RL_PEEK_NIL = 4u,
+  RL_PEEK_PER_SECOND = 8u,
+  RL_PEEK_BAD = 16u
+};
+typedef struct rl_peek_reply { /* 16 B */
+  uint32_t count;    /* GET: the counter INCRBY would add to (0 when not found) */
+  uint32_t ttl_s;    /* main store: expiry second - now (> 0 when found); per-second store: 0 (the table keeps
+                        no TTL for it) */
+  uint32_t cached_s; /* local over-limit cache: deadline - now when LOCAL_CACHED, else 0 */
+  uint32_t flags;    /* RL_PEEK_* */
+} rl_peek_reply;
+int rl_peek(rl_engine* e, const rl_batch* host_batch, rl_peek_reply* out);
+int rl_peek_device(rl_engine* e, const rl_batch* device_batch, rl_peek_reply* d_out);
+int rl_forget(rl_engine* e, const rl_batch* host_batch, rl_peek_reply* out_or_null);
+
 /* ---- Descriptor-tree resolution (GetLimit) ------------------------
  * Replaces rateLimitConfigImpl.GetLimit (src/config/config_impl.go:274-323) per descriptor,
  * batched on the device: it yields the rule id each descriptor of an rl_batch carries.
