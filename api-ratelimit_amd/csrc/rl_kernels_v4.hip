@@ -51,9 +51,10 @@ constexpr unsigned long long HS_SUM_MASK = (1ull << HS_CNT_SHIFT) - 1ull;
 static_assert((unsigned long long)V4_TILE * 0xFFFFFFFFull <= HS_SUM_MASK && V4_TILE < (1 << 12), "hot word fields");
 static_assert(ROW >= NBUCKETS + 1, "row holds every bucket start and the end");
 #ifndef RL_G_CAP
-// 896 records (two average config-3 buckets) per LDS stage at 3 blocks per CU (50 KB LDS,
-// 152 VGPRs, no spills) measured 114.5 us/step against 118.5 for 640 x 4 blocks (spilling at
-// 128 VGPRs) and 134.6 for 1024 x 2 (tools/build_variants.sh, bench --lib, one box)
+// 896 records (the whole buckets k4_scan packs into one range) per LDS stage at 3 blocks per CU
+// (then 50 KB LDS and 152 VGPRs, no spills; 52 KB with the packed slot words) measured
+// 114.5 us/step against 118.5 for 640 x 4 blocks (spilling at 128 VGPRs) and 134.6 for
+// 1024 x 2 (tools/build_variants.sh, bench --lib, one box)
 #define RL_G_CAP 896
 #define RL_G_HASH 1024
 #define RL_G_OCC 3
@@ -868,8 +869,9 @@ struct GS {
   uint16_t* list;  // positions grouped by key, each key's in position (= arrival) order
   uint16_t* grp;   // position -> hash slot
   uint32_t* slot;  // hash slot -> first position inserted with the key (G_EMPTY = free)
-  uint32_t* cnt;   // hash slot -> records of the key
-  uint16_t* end;   // hash slot -> end of the key's list (start = end - cnt)
+  uint32_t* cnt;   // hash slot -> records of the key (global scratch only)
+  uint16_t* end;   // hash slot -> end of the key's list (start = end - cnt; global scratch only)
+  unsigned long long* pk;  // hash slot -> packed word (LDS only): see PK_BITS
   uint32_t* cursor;
   uint32_t hs;     // hash slots (power of two)
 };
@@ -890,7 +892,71 @@ RL_DEV void gbar() {
 // differs from the first record's, CNT_MIXED_UNIT when its unit does too (found here, in
 // parallel, instead of by a walk of the key's list).
 constexpr uint32_t CNT_MASK = 0xFFFFu, CNT_MIXED = 0x10000u, CNT_MIXED_UNIT = 0x20000u;
-RL_DEV bool g_insert(const GS& g, uint32_t k, const DevRule* __restrict__ rules) {
+
+// The LDS path keeps one u64 per hash slot in place of cnt and end, so that all G_W waves can
+// lay out the lists at once: the staged positions [0, m) are cut into G_W parts of whole
+// 64-position chunks (part w = chunks [w * cpw, (w + 1) * cpw), cpw = ceil(m / (64 * G_W))), and
+// the word holds one PK_BITS field per part, the key's total and the two flags:
+//   bits [11 w, 11 w + 11)  part w: the key's records in the part (insert), then the start of
+//                           the part's piece of the key's list (reserve), then its end (layout)
+//   bits [44, 55)           records of the key
+//   bit 55 / 56             CNT_MIXED / CNT_MIXED_UNIT
+// A key's list is its parts' pieces in part order, so it stays in position (= arrival) order;
+// after the layout field G_W - 1 is the end of the list. No field carries into the next: a
+// count and a cursor never pass m <= G_CAP < 2^11, and each wave adds to its own field only.
+constexpr int PK_BITS = 11;
+constexpr unsigned long long PK_MASK = (1ull << PK_BITS) - 1ull;
+constexpr int PK_TOT_SHIFT = PK_BITS * G_W;
+constexpr unsigned long long PK_MIXED = 1ull << (PK_TOT_SHIFT + PK_BITS), PK_MIXED_UNIT = PK_MIXED << 1;
+constexpr unsigned long long PK_KEEP = ~((1ull << PK_TOT_SHIFT) - 1ull);  // total and flags
+static_assert(PK_TOT_SHIFT + PK_BITS + 2 <= 64 && (unsigned long long)G_CAP <= PK_MASK, "packed slot word");
+constexpr uint32_t pk_field(unsigned long long w, int p) { return (uint32_t)(w >> (PK_BITS * p)) & (uint32_t)PK_MASK; }
+constexpr uint32_t pk_total(unsigned long long w) { return (uint32_t)(w >> PK_TOT_SHIFT) & (uint32_t)PK_MASK; }
+// chunks per part, and the part of chunk c = c / cpw by a multiply (cpw <= PK_CPW_MAX)
+constexpr uint32_t PK_CPW_MAX = (G_CAP + 64 * G_W - 1) / (64 * G_W);
+constexpr uint32_t pk_cpw(uint32_t m) { return (m + 64u * G_W - 1u) / (64u * G_W); }
+constexpr uint32_t pk_inv(uint32_t cpw) { return (256u + cpw - 1u) / cpw; }
+constexpr uint32_t pk_part(uint32_t c, uint32_t inv) { return (c * inv) >> 8; }
+constexpr bool pk_part_ok() {
+  for (uint32_t cpw = 1; cpw <= PK_CPW_MAX; ++cpw)
+    for (uint32_t c = 0; c < cpw * G_W; ++c)
+      if (pk_part(c, pk_inv(cpw)) != c / cpw) return false;
+  return true;
+}
+static_assert(pk_part_ok(), "part of a chunk by multiply");
+// reserve: the per-part counts of a slot's word become per-part starts from `run` on
+constexpr unsigned long long pk_reserve(unsigned long long w, uint32_t run) {
+  unsigned long long nw = w & PK_KEEP;
+  for (int p = 0; p < G_W; ++p) {
+    nw |= (unsigned long long)run << (PK_BITS * p);
+    run += pk_field(w, p);
+  }
+  return nw;
+}
+static_assert(pk_reserve((3ull << PK_TOT_SHIFT) | PK_MIXED | (2ull << (PK_BITS * (G_W - 1))) | 1ull, 893u) ==
+                  ((3ull << PK_TOT_SHIFT) | PK_MIXED | (894ull << (PK_BITS * (G_W - 1))) |
+                   (G_W > 2 ? (894ull << PK_BITS) | (G_W > 3 ? 894ull << (2 * PK_BITS) : 0ull) : 0ull) | 893ull),
+              "reserve keeps total and flags and chains the parts");
+
+// A key's list as the phases after the layout read it.
+struct KeyList {
+  uint32_t end, n;  // list[end - n, end)
+  bool mixed, mixed_unit;
+};
+template <bool LDS>
+RL_DEV KeyList g_key(const GS& g, uint32_t s) {
+  if constexpr (LDS) {
+    const unsigned long long w = g.pk[s];
+    return KeyList{pk_field(w, G_W - 1), pk_total(w), (w & PK_MIXED) != 0, (w & PK_MIXED_UNIT) != 0};
+  } else {
+    const uint32_t cw = g.cnt[s];
+    return KeyList{g.end[s], cw & CNT_MASK, (cw & CNT_MIXED) != 0, (cw & CNT_MIXED_UNIT) != 0};
+  }
+}
+
+// inv: pk_inv of the range's chunks per part (LDS path)
+template <bool LDS>
+RL_DEV bool g_insert(const GS& g, uint32_t k, const DevRule* __restrict__ rules, uint32_t inv) {
   // identity: the sort key and the tag (fp_lo's low half; its high half is the record's jitter)
   const uint64_t key = g.rec[k].key;
   const uint32_t lo = (uint32_t)g.rec[k].fp_lo;
@@ -921,12 +987,46 @@ RL_DEV bool g_insert(const GS& g, uint32_t k, const DevRule* __restrict__ rules)
     const uint32_t r0 = rule_of(g.rec[v].rn), r1 = rule_of(g.rec[k].rn);
     if (r0 != r1) inc |= rules[r0].unit != rules[r1].unit ? (CNT_MIXED | CNT_MIXED_UNIT) : CNT_MIXED;
   }
-  if (inc == 1u) atomicAdd(&g.cnt[s], 1u);
-  else atomicOr(&g.cnt[s], inc & ~1u), atomicAdd(&g.cnt[s], 1u);
+  if constexpr (LDS) {
+    // one to the position's part and one to the total, in a single add
+    if (inc != 1u) atomicOr(&g.pk[s], (inc & CNT_MIXED_UNIT) ? (PK_MIXED | PK_MIXED_UNIT) : PK_MIXED);
+    atomicAdd(&g.pk[s], (1ull << (PK_BITS * pk_part(k >> 6, inv))) + (1ull << PK_TOT_SHIFT));
+  } else {
+    if (inc == 1u) atomicAdd(&g.cnt[s], 1u);
+    else atomicOr(&g.cnt[s], inc & ~1u), atomicAdd(&g.cnt[s], 1u);
+  }
   return v == G_EMPTY;  // this position claimed the hash slot: it leads the key
 }
 
-// One wave: each key's list in position order (positions [0, m), 64 at a time).
+// LDS path, every wave: wave w lays out part w (chunks [w * cpw, (w + 1) * cpw)) chunk by chunk.
+// The first lane of each group of equal slots in a chunk adds the group's size to the slot's
+// field w and gets the group's base back; the waves' adds touch different fields and commute.
+RL_DEV void g_layout_parts(const GS& g, uint32_t m, uint32_t cpw) {
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t lt = lanemask_lt();
+  const int sh = PK_BITS * (int)wave;
+  const uint32_t c0 = wave * cpw * 64u, c1 = min(m, c0 + cpw * 64u);
+  for (uint32_t c = c0; c < c1; c += 64) {
+    const uint32_t k = c + lane;
+    const bool valid = k < m;
+    const uint32_t s = valid ? g.grp[k] : 0u;
+    uint64_t mm = __ballot(valid);
+#pragma unroll
+    for (int b = 0; (G_HASH >> b) > 1; ++b) {
+      const bool bit = (s >> b) & 1u;
+      const uint64_t bal = __ballot(bit);
+      mm &= bit ? bal : ~bal;
+    }
+    const uint32_t first = valid ? (uint32_t)__ffsll((unsigned long long)mm) - 1u : lane;
+    uint32_t base = 0;
+    if (valid && lane == first)
+      base = (uint32_t)(atomicAdd(&g.pk[s], (unsigned long long)__popcll(mm) << sh) >> sh) & (uint32_t)PK_MASK;
+    base = (uint32_t)__shfl((int)base, (int)first, 64);
+    if (valid) g.list[base + (uint32_t)__popcll(mm & lt)] = (uint16_t)k;
+  }
+}
+
+// Global scratch, one wave: each key's list in position order (positions [0, m), 64 at a time).
 RL_DEV void g_layout(const GS& g, uint32_t m) {
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t lt = lanemask_lt();
@@ -980,7 +1080,8 @@ RL_DEV void g_scan(const GS& g, uint32_t m, LSeg* s_agg, LSeg* s_carry) {
         const uint32_t k = g.list[e];
         const uint32_t s = g.grp[k];
         pos[q] = k;
-        hd[q] = e == (uint32_t)g.end[s] - (g.cnt[s] & CNT_MASK);
+        const KeyList kl = g_key<LDS>(g, s);
+        hd[q] = e == kl.end - kl.n;
         hv[q] = g.rec[k].h;
         t = lseg_op(t, LSeg{hd[q], hv[q]});
       }
@@ -1018,17 +1119,20 @@ RL_DEV void g_scan(const GS& g, uint32_t m, LSeg* s_agg, LSeg* s_carry) {
   }
 }
 
-RL_DEV uint32_t g_tail(const GS& g, uint32_t k) { return g.list[g.end[g.grp[k]] - 1u]; }
+template <bool LDS>
+RL_DEV uint32_t g_tail(const GS& g, uint32_t k) { return g.list[g_key<LDS>(g, g.grp[k]).end - 1u]; }
 
 // The exact sequential path of a key (rare: a string shared by units of different sizes
 // whose expiry falls inside the batch), run by its leader in a pass after the leaders' so
 // its registers are not live across the fast path's. rec[k].key holds the key's slot.
 constexpr uint32_t SEG_EXOTIC_PENDING = 0xFFFFFFFCu;
+template <bool LDS>
 RL_DEV void g_lead_exotic(const GS& g, uint32_t k, const DevRule* __restrict__ rules, const TableDesc& tab,
                           EngineCtl* ctl) {
   Slot* slot = reinterpret_cast<Slot*>(g.rec[k].key);
   const uint32_t s = g.grp[k];
-  const uint32_t n = g.cnt[s] & CNT_MASK, e0 = g.end[s] - n;
+  const KeyList kl = g_key<LDS>(g, s);
+  const uint32_t n = kl.n, e0 = kl.end - n;
   const uint32_t region = key_region(slot->key);
   const uint32_t ws = region_ws(region, ctl->gen_max[region]);
   KeyState ks = read_state(slot);
@@ -1049,6 +1153,7 @@ RL_DEV void g_lead_exotic(const GS& g, uint32_t k, const DevRule* __restrict__ r
 // Leaves the counter before the batch in rec[k].key and the freeze in rec[k].fp_lo; an exotic
 // key (a string shared by units of different sizes whose expiry falls inside the batch)
 // leaves per-position replies in P (SEG_EXOTIC). New slots are counted per region in ins[].
+template <bool LDS>
 RL_DEV void g_lead(const GS& g, uint32_t k, const DevRule* __restrict__ rules, const TableDesc& tab, HotCand* cand,
                    EngineCtl* ctl, const uint32_t* s_gen, bool has_pre, const SlotView& pre, int cand_on,
                    uint32_t& heads, uint64_t& ins) {
@@ -1057,10 +1162,10 @@ RL_DEV void g_lead(const GS& g, uint32_t k, const DevRule* __restrict__ rules, c
   const uint64_t key = g.rec[k].key, lo = g.rec[k].fp_lo;
   const uint32_t rule = rule_of(g.rec[k].rn);
   const uint32_t s = g.grp[k];
-  const uint32_t cw = g.cnt[s];
-  const uint32_t n = cw & CNT_MASK, e1 = g.end[s], e0 = e1 - n;
+  const KeyList kl = g_key<LDS>(g, s);
+  const uint32_t n = kl.n, e1 = kl.end, e0 = e1 - n;
   const uint32_t tail = g.list[e1 - 1];
-  const bool mixed = (cw & CNT_MIXED) != 0, mixed_unit = (cw & CNT_MIXED_UNIT) != 0;
+  const bool mixed = kl.mixed, mixed_unit = kl.mixed_unit;
   const uint64_t Pk = g.P[tail];
   const DevRule R0 = rules[rule];
   heads += 1;
@@ -1160,10 +1265,11 @@ RL_DEV uint32_t group_range(const GS& g, uint32_t m, const DevRule* __restrict__
   static_assert(KPT <= 8 && G_IPT <= KPT, "owner bits");
   uint32_t own = 0;  // bit j: position tid + j * G_NT leads its key
   SlotView pre[G_IPT];
+  const uint32_t cpw = pk_cpw(m), inv = pk_inv(cpw);  // LDS path: chunks per part (wave)
 #pragma unroll
   for (int j = 0; j < KPT; ++j) {
     const uint32_t k = tid + j * G_NT;
-    if (k < m && g_insert(g, k, rules)) own |= 1u << j;
+    if (k < m && g_insert<LDS>(g, k, rules, inv)) own |= 1u << j;
   }
   if constexpr (LDS) {
     // every thread issues G_IPT slot loads at once, a position that leads no key reading the
@@ -1179,7 +1285,26 @@ RL_DEV uint32_t group_range(const GS& g, uint32_t m, const DevRule* __restrict__
   gbar<LDS>();
   ST4(1);
   // each key's list start: exclusive prefix of the per-slot counts (hash-slot order)
-  {
+  if constexpr (LDS) {
+    // the same prefix over the slots' totals; each slot's per-part counts become the starts of
+    // its parts' pieces (pk_reserve)
+    constexpr uint32_t SPT = G_HASH / G_NT;
+    const uint32_t s0 = tid * SPT;
+    unsigned long long w[SPT];
+    uint32_t sum = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < SPT; ++q) {
+      w[q] = g.pk[s0 + q];
+      sum += pk_total(w[q]);
+    }
+    uint32_t tot;
+    uint32_t run = tile::block_excl_scan<G_NT>(sum, sh_w, tot);
+#pragma unroll
+    for (uint32_t q = 0; q < SPT; ++q) {
+      g.pk[s0 + q] = pk_reserve(w[q], run);
+      run += pk_total(w[q]);
+    }
+  } else {
     const uint32_t spt = g.hs / G_NT, s0 = tid * spt;
     uint32_t sum = 0;
     for (uint32_t q = 0; q < spt; ++q) sum += g.cnt[s0 + q] & CNT_MASK;
@@ -1192,7 +1317,8 @@ RL_DEV uint32_t group_range(const GS& g, uint32_t m, const DevRule* __restrict__
   }
   gbar<LDS>();
   ST4(6);
-  if (wave == 0) g_layout(g, m);
+  if constexpr (LDS) g_layout_parts(g, m, cpw);
+  else if (wave == 0) g_layout(g, m);
   gbar<LDS>();
   ST4(7);
   g_scan<LDS>(g, m, s_agg, s_carry);
@@ -1201,24 +1327,26 @@ RL_DEV uint32_t group_range(const GS& g, uint32_t m, const DevRule* __restrict__
   if constexpr (LDS) {
 #pragma unroll
     for (int j = 0; j < G_IPT; ++j)
-      if ((own >> j) & 1u) g_lead(g, tid + j * G_NT, rules, tab, cand, ctl, s_gen, true, pre[j], cand_on, heads, ins);
+      if ((own >> j) & 1u)
+        g_lead<LDS>(g, tid + j * G_NT, rules, tab, cand, ctl, s_gen, true, pre[j], cand_on, heads, ins);
   } else {
 #pragma unroll
     for (int j = 0; j < KPT; ++j)
       if ((own >> j) & 1u)
-        g_lead(g, tid + j * G_NT, rules, tab, cand, ctl, s_gen, false, SlotView{}, cand_on, heads, ins);
+        g_lead<LDS>(g, tid + j * G_NT, rules, tab, cand, ctl, s_gen, false, SlotView{}, cand_on, heads, ins);
   }
   __threadfence_block();
   __syncthreads();
   // exotic keys (rare): their leaders' sequential pass
   for (uint32_t k = tid; k < m; k += G_NT)
-    if ((uint32_t)g.rec[k].fp_lo == SEG_EXOTIC_PENDING && g_tail(g, k) == k) g_lead_exotic(g, k, rules, tab, ctl);
+    if ((uint32_t)g.rec[k].fp_lo == SEG_EXOTIC_PENDING && g_tail<LDS>(g, k) == k)
+      g_lead_exotic<LDS>(g, k, rules, tab, ctl);
   __threadfence_block();
   __syncthreads();
   ST4(4);
   for (uint32_t k = tid; k < m; k += G_NT) {
     const MRec x = g.rec[k];
-    const uint32_t t = g_tail(g, k);
+    const uint32_t t = g_tail<LDS>(g, k);
     const MRec& lt = g.rec[t];
     tile::decide_at(x.idx, x.req, rule_of(x.rn), x.h, x.rn >> V4_RULE_BITS, lt.key, g.P[k], (uint32_t)lt.fp_lo, rules,
                   out, req_thr, routed);
@@ -1442,8 +1570,8 @@ __global__ __launch_bounds__(G_NT, RL_G_OCC) void k4_group(DevBatch in,
   __shared__ uint16_t s_list[G_CAP];
   __shared__ uint16_t s_grp[G_CAP];
   __shared__ uint32_t s_slot[G_HASH];
-  __shared__ uint32_t s_cnt[G_HASH];
-  __shared__ uint16_t s_end[G_HASH];
+  __shared__ unsigned long long s_pk[G_HASH];
+  uint32_t* const s_cnt = reinterpret_cast<uint32_t*>(s_pk);  // the last block's sums (no range then)
   __shared__ LSeg s_agg[G_W];
   __shared__ LSeg s_carry;
   __shared__ uint32_t s_cursor, s_heads, s_last, s_err;
@@ -1491,7 +1619,7 @@ __global__ __launch_bounds__(G_NT, RL_G_OCC) void k4_group(DevBatch in,
       if (split_half < 0) {  // whole buckets: at most G_CAP records (k4_scan's packing)
         for (uint32_t s = tid; s < (uint32_t)G_HASH; s += G_NT) {
           s_slot[s] = G_EMPTY;
-          s_cnt[s] = 0;
+          s_pk[s] = 0;
         }
         if (tid == 0) s_cursor = 0;
         const uint32_t m = gather_runs<G_IPT, G_CAP>(srec, tstart, ntiles, B0, B1, s_rec, s_ra, s_pre, sh_w);
@@ -1502,7 +1630,7 @@ __global__ __launch_bounds__(G_NT, RL_G_OCC) void k4_group(DevBatch in,
         }
         __syncthreads();
         ST4(2);
-        const GS gl{s_rec, s_P, s_list, s_grp, s_slot, s_cnt, s_end, &s_cursor, G_HASH};
+        const GS gl{s_rec, s_P, s_list, s_grp, s_slot, nullptr, nullptr, s_pk, &s_cursor, G_HASH};
         {
           const uint32_t hh = group_range<true>(gl, m, rules, tab, out, req_thr, cand, cand_on, routed, s_agg,
                                                 &s_carry, sh_w, ins, ctl, s_gen);
@@ -1536,7 +1664,7 @@ __global__ __launch_bounds__(G_NT, RL_G_OCC) void k4_group(DevBatch in,
           __syncthreads();  // the previous half is done with LDS
           for (uint32_t s = tid; s < (uint32_t)G_HASH; s += G_NT) {
             s_slot[s] = G_EMPTY;
-            s_cnt[s] = 0;
+            s_pk[s] = 0;
           }
           // compact the half's records in position (= arrival) order: one block scan per
           // 256-position chunk
@@ -1552,7 +1680,7 @@ __global__ __launch_bounds__(G_NT, RL_G_OCC) void k4_group(DevBatch in,
           if (tid == 0) s_cursor = 0;
           __syncthreads();
           if (mp == 0) continue;
-          const GS gl{s_rec, s_P, s_list, s_grp, s_slot, s_cnt, s_end, &s_cursor, G_HASH};
+          const GS gl{s_rec, s_P, s_list, s_grp, s_slot, nullptr, nullptr, s_pk, &s_cursor, G_HASH};
           heads += group_range<true>(gl, mp, rules, tab, out, req_thr, cand, cand_on, routed, s_agg, &s_carry,
                                      sh_w, ins, ctl, s_gen);
         }
@@ -1562,8 +1690,8 @@ __global__ __launch_bounds__(G_NT, RL_G_OCC) void k4_group(DevBatch in,
         const GS gg{src,                              gs.P + (size_t)j * BUCKET_CAP,
                     gs.list + (size_t)j * BUCKET_CAP,  gs.grp + (size_t)j * BUCKET_CAP,
                     gs.slot + (size_t)j * GS_HASH,     gs.cnt + (size_t)j * GS_HASH,
-                    gs.end + (size_t)j * GS_HASH,      gs.cursor + j,
-                    GS_HASH};
+                    gs.end + (size_t)j * GS_HASH,      nullptr,
+                    gs.cursor + j,                     GS_HASH};
         for (uint32_t s = tid; s < (uint32_t)GS_HASH; s += G_NT) {
           gg.slot[s] = G_EMPTY;
           gg.cnt[s] = 0;
