@@ -275,6 +275,67 @@ void HipRateLimitCache::Load(const std::string& path) {
   });
 }
 
+void HipRateLimitCache::Resize(const uint32_t log2_slots[4]) {
+  uint32_t lg[4];
+  for (int u = 0; u < 4; ++u) lg[u] = log2_slots[u];
+  control([this, lg]() -> std::string { return rl_resize(eng_, lg) ? rl_last_error(eng_) : ""; });
+}
+
+rl_occupancy HipRateLimitCache::Occupancy() {
+  rl_occupancy o;
+  memset(&o, 0, sizeof o);
+  control([this, &o]() -> std::string { return rl_get_occupancy(eng_, &o) ? rl_last_error(eng_) : ""; });
+  return o;
+}
+
+// Auto-grow (rl_cache.hpp Resize), after a completed batch: while a home unit is over the
+// watermark and below its maximum, complete what is in flight and double it. The occupancy is
+// the host mirror's (no device call). This engine is a lone one (no lag window), so a region
+// keeps no previous generation: live is all it holds.
+void HipRateLimitCache::autogrow(std::deque<Staged>& inflight) {
+  if (!s_.autogrow_permille) return;
+  for (;;) {
+    rl_occupancy o;
+    if (rl_get_occupancy(eng_, &o)) return;
+    uint32_t lg[4] = {0, 0, 0, 0}, used[4];
+    bool any = false;
+    for (int u = 0; u < 4; ++u) {
+      used[u] = std::max(o.live[2 * u], o.live[2 * u + 1]);
+      uint32_t log2 = 0;
+      while ((1u << log2) < o.slots[2 * u]) ++log2;
+      if ((uint64_t)used[u] * 1000u <= (uint64_t)o.slots[2 * u] * s_.autogrow_permille) continue;
+      if (log2 >= s_.max_log2_slots[u] || log2 >= 31u) continue;
+      if (grow_failed_at_[u] && used[u] <= grow_failed_at_[u]) continue;  // not before occupancy rises again
+      lg[u] = log2 + 1;
+      any = true;
+    }
+    if (!any) return;
+    if (!inflight.empty()) {
+      while (!inflight.empty()) {
+        finish(inflight.front());
+        inflight.pop_front();
+      }
+      n_drains_ += 1;
+      continue;  // the drained batches moved the occupancy: decide on what it is now
+    }
+    if (rl_resize(eng_, lg)) {
+      n_resize_fail_ += 1;
+      for (int u = 0; u < 4; ++u)
+        if (lg[u]) grow_failed_at_[u] = used[u];
+      return;
+    }
+    n_resizes_ += 1;
+    for (int u = 0; u < 4; ++u)
+      if (lg[u]) grow_failed_at_[u] = 0;
+  }
+}
+
+void HipRateLimitCache::finish_oldest(std::deque<Staged>& inflight) {
+  finish(inflight.front());
+  inflight.pop_front();
+  autogrow(inflight);
+}
+
 // Peek / Forget: the request's descriptors as one rl_batch of one request, built and handed to
 // rl_peek / rl_forget by the submitter thread (a control call), at the time it reads there.
 std::vector<HipRateLimitCache::PeekStatus> HipRateLimitCache::peek_call(
@@ -637,8 +698,7 @@ void HipRateLimitCache::submitter() {
       std::unique_lock<std::mutex> g(mu_);
       if (!inflight.empty() && q_.empty()) {
         g.unlock();
-        finish(inflight.front());
-        inflight.pop_front();
+        finish_oldest(inflight);
         continue;
       }
       cv_.wait(g, [&] { return stop_ || !q_.empty(); });
@@ -650,6 +710,7 @@ void HipRateLimitCache::submitter() {
       // every call enqueued before it is decided and answered; the engine is idle
       for (auto& st : inflight) finish(st);
       inflight.clear();
+      autogrow(inflight);
       const std::string msg = first->ctl();
       if (msg.empty()) first->done.set_value();
       else first->done.set_exception(std::make_exception_ptr(RedisError("hip backend: " + msg)));
@@ -693,10 +754,7 @@ void HipRateLimitCache::submitter() {
           // its batch's own, not that plus the next batch's window
           g.unlock();
           const int qr = rl_query(eng_);
-          if (qr == 1) {
-            finish(inflight.front());
-            inflight.pop_front();
-          }
+          if (qr == 1) finish_oldest(inflight);
           g.lock();
           if (qr == 1) continue;
           const auto slice = std::min(deadline, std::chrono::steady_clock::now() + std::chrono::microseconds(10));
@@ -710,10 +768,7 @@ void HipRateLimitCache::submitter() {
     }
     submit(st, inflight);
     inflight.push_back(std::move(st));
-    if (inflight.size() == 2) {
-      finish(inflight.front());
-      inflight.pop_front();
-    }
+    if (inflight.size() == 2) finish_oldest(inflight);
   }
   for (auto& st : inflight) finish(st);
 }

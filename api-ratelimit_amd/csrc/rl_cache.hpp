@@ -167,6 +167,12 @@ struct HipSettings {
   uint32_t batch_limit = 1u << 16;        // HIP_BATCH_LIMIT (descriptors)
   uint64_t hash_seed = 0x5ee7ab1e5eedull;  // HIP_HASH_SEED: the same in every process of a deployment
   uint32_t max_load_permille = 750;        // HIP_TABLE_MAX_LOAD: refuse a batch past this region load
+  // HIP_TABLE_AUTOGROW (0 = off, the default): once a completed batch leaves either parity region
+  // of a home unit with more than slots * autogrow_permille / 1000 live slots, the single-engine
+  // batcher doubles that unit's regions (rl_resize), up to 2^max_log2_slots[unit]
+  // (HIP_TABLE_MAX_SLOTS). HipRateLimitCache::Resize below.
+  uint32_t autogrow_permille = 0;
+  uint32_t max_log2_slots[4] = {31, 31, 31, 31};
   bool answer_early = true;                // HIP_BATCH_ANSWER_EARLY: while gathering, answer the batch in
                                            // flight as soon as the device is done with it (rl_query)
   // EXPIRATION_JITTER_MAX_SECONDS (settings.go:43, default 300; at most 65536 here): every INCRBY's
@@ -226,17 +232,43 @@ class HipRateLimitCache : public RateLimitCache {
   std::vector<PeekStatus> Forget(const RateLimitRequest& request,
                                  const std::vector<std::shared_ptr<RateLimit>>& limits);
 
+  // Resize (rl_hip.h "Resize"): the counter table moved into one of log2_slots[u] slots per window
+  // generation for home unit u (0 keeps that unit's size), on the device, every counter kept. A
+  // control call like Save / Load: every DoLimit enqueued before it is decided first, rl_resize
+  // runs on the submitter thread with nothing in flight, DoLimit callers are held for the pass.
+  // A refusal throws RedisError and changes nothing (a shrink is checked against the occupancy
+  // mirror, which may over-count: a tight one can be refused although it would fit). Peak device
+  // memory is the old table plus the new one. Occupancy is rl_get_occupancy at the same point of
+  // the serial order.
+  // Auto-grow (HipSettings::autogrow_permille > 0): after every completed batch the submitter
+  // reads rl_get_occupancy; if either parity region of a home unit holds more than
+  // slots * autogrow_permille / 1000 live slots and the unit is below 2^max_log2_slots[unit], it
+  // completes the batches in flight (counted in drains) and calls rl_resize with that unit's
+  // log2 + 1. With the watermark below HIP_TABLE_MAX_LOAD the table therefore grows before a
+  // batch is refused; no batch is retried or reordered. A single batch that takes a region from
+  // under the watermark to over its load limit is still refused as without auto-grow (its callers
+  // get RedisError), and the growth follows it. A grow that fails (no device memory for the two
+  // tables) is counted in resize_failures and not tried again until that unit's occupancy has
+  // risen; the old table keeps serving and DoLimit never throws because of it.
+  // Out of scope: HipRoutedRateLimitCache (every rank would have to resize between the same two
+  // steps; rl_resize itself is legal on a router's engine between steps) and a resize while
+  // batches are in flight.
+  void Resize(const uint32_t log2_slots[4]);
+  rl_occupancy Occupancy();
+
   // Batcher counters (tests): batches submitted, rule-table loads, and loads made while an
   // earlier batch was still in flight (append-only rule table, rl_hip.h rl_load_rules).
   // drains: times the batches in flight were completed early so that a rule-table load or a
   // submit the engine refused with them in flight (RL_ESTATE) could be made.
   // compact_batches: batches sent in the compact wire format (rl_submit_c); the others went as
   // rl_batch (a rule id past 0xFFFE, a prefix past 65535 bytes or hits_addend past 2^24 - 1).
+  // resizes / resize_failures: auto-grow's rl_resize calls that succeeded / failed.
   struct BatcherStats {
-    uint64_t batches, rule_loads, rule_loads_in_flight, drains, compact_batches;
+    uint64_t batches, rule_loads, rule_loads_in_flight, drains, compact_batches, resizes, resize_failures;
   };
   BatcherStats batcher_stats() const {
-    return {n_batches_.load(), n_loads_.load(), n_loads_inflight_.load(), n_drains_.load(), n_compact_.load()};
+    return {n_batches_.load(), n_loads_.load(),   n_loads_inflight_.load(), n_drains_.load(),
+            n_compact_.load(), n_resizes_.load(), n_resize_fail_.load()};
   }
   // (tests) set before the first DoLimit
   void set_trace(TraceFn f) { trace_ = std::move(f); }
@@ -255,6 +287,8 @@ class HipRateLimitCache : public RateLimitCache {
   void add(Staged& st, const std::shared_ptr<PendingCall>& c);
   void submit(Staged& st, std::deque<Staged>& inflight);
   void finish(Staged& st);
+  void finish_oldest(std::deque<Staged>& inflight);
+  void autogrow(std::deque<Staged>& inflight);
   void fail(std::vector<std::shared_ptr<PendingCall>>& calls);
   void done_calls(size_t n);
 
@@ -273,6 +307,8 @@ class HipRateLimitCache : public RateLimitCache {
   std::vector<rl_rule> rules_;
   bool rules_dirty_ = false;
   std::atomic<uint64_t> n_batches_{0}, n_loads_{0}, n_loads_inflight_{0}, n_drains_{0}, n_compact_{0};
+  std::atomic<uint64_t> n_resizes_{0}, n_resize_fail_{0};
+  uint32_t grow_failed_at_[4] = {0, 0, 0, 0};  // live slots of the unit when its last grow failed (0 = none)
   // statuses of a compact batch made on the host from its raw replies (rl_decide_raw)
   std::vector<rl_status> dec_out_;
   std::vector<uint32_t> dec_thr_;

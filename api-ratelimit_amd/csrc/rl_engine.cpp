@@ -1970,6 +1970,95 @@ int rl_restore_end(rl_engine* e) {
   return 0;
 }
 
+// ---- Resize -------------------------------------------------------------------------------
+// Every check comes before anything changes, the new table is built beside the old one, and the
+// engine's fields are swapped only after the device pass has been read back clean: a failure of
+// any kind leaves the old table in service. Nothing but `table` / `tab` holds a table address
+// across batches: every kernel takes TableDesc by value at its launch, HotBucket.slot (v4_hb) is
+// rewritten by k4_scan at the start of every batch and k4_group's scratch is per batch, so with
+// nothing in flight there is nothing to invalidate. The hot set and the candidate stash hold key
+// prefixes and stay.
+int rl_resize(rl_engine* e, const uint32_t log2_slots[4]) {
+  if (!e || !log2_slots) return RL_EINVAL;
+  if (e->n_fl) return e->fail(RL_ESTATE, "rl_resize while a batch is in flight (call rl_wait)");
+  if (e->restoring) return e->fail(RL_ESTATE, "rl_resize between rl_restore_begin and rl_restore_end");
+  uint32_t lg4[4];
+  for (int u = 0; u < 4; ++u) {
+    lg4[u] = log2_slots[u] ? log2_slots[u] : e->cfg.log2_slots[u];
+    if (lg4[u] < 4 || lg4[u] > 31) return e->fail(RL_EINVAL, "rl_resize: log2_slots[%d] = %u outside 4..31", u, lg4[u]);
+  }
+  TableDesc nt = e->tab;
+  RegionOcc nocc[8];
+  size_t off = 0;
+  for (int r = 0; r < 8; ++r) {
+    const uint32_t lg = lg4[r / 2];
+    nt.region_base[r] = off;
+    nt.region_log2[r] = lg;
+    off += (size_t)1 << lg;
+    nocc[r] = e->occ[r];
+    nocc[r].limit = (uint32_t)(((uint64_t)1 << lg) * e->cfg.max_load_permille / 1000);
+    // the mirror never under-counts (rl_common.h occ_advance), so what passes here fits
+    if ((uint64_t)e->occ[r].live + e->occ[r].prev > nocc[r].limit)
+      return e->fail(RL_ENOSPC, "rl_resize: region %d holds %llu slots by its occupancy, over the new load limit of %u "
+                                "(2^%u slots)",
+                     r, (unsigned long long)e->occ[r].live + e->occ[r].prev, nocc[r].limit, lg);
+  }
+  int rc = e->snap_alloc();
+  if (rc) return rc;
+  Slot* nbuf = nullptr;
+  hipError_t he = hipMalloc(&nbuf, off * sizeof(Slot));
+  if (he != hipSuccess) {
+    (void)hipGetLastError();
+    return e->fail(RL_EHIP, "rl_resize: no room for the new table of %llu slots beside the old one: %s",
+                   (unsigned long long)off, hipGetErrorString(he));
+  }
+  nt.slots = nbuf;
+  SnapGens g;
+  for (int r = 0; r < 8; ++r) g.gen[r] = e->occ[r].gen;
+  he = hipMemsetAsync(nbuf, 0, off * sizeof(Slot), e->stream);
+  if (he == hipSuccess) he = hipMemsetAsync(e->d_snap_ctl, 0, sizeof(SnapCtl), e->stream);
+  if (he == hipSuccess) {
+    launch_rehash(e->stream, e->tab, e->table_slots, g, nt, e->d_snap_ctl);
+    he = hipGetLastError();
+  }
+  if (he == hipSuccess)
+    he = hipMemcpyAsync(e->h_snap_ctl, e->d_snap_ctl, sizeof(SnapCtl), hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  if (he != hipSuccess) {
+    hipFree(nbuf);
+    return e->hip_fail(he, "rl_resize");
+  }
+  const uint32_t errs = e->h_snap_ctl->err;
+  const char* why = nullptr;
+  if (errs & SNAP_ERR_FULL) why = "a region of the new table had no free slot left";
+  else if (errs & SNAP_ERR_DUP) why = "an identity occurs twice in the old table";
+  else if (errs) why = "a live slot lies outside its key's region";
+  for (int r = 0; r < 8 && !why; ++r) {
+    nocc[r].live = e->h_snap_ctl->cnt[2 * r][0];
+    nocc[r].prev = e->h_snap_ctl->cnt[2 * r + 1][0];
+    if ((uint64_t)nocc[r].live + nocc[r].prev > (uint64_t)e->occ[r].live + e->occ[r].prev)
+      why = "the table holds more live slots than its occupancy says";
+  }
+  if (why) {
+    hipFree(nbuf);
+    return e->fail(RL_EDEVICE, "rl_resize: %s; the old table is untouched", why);
+  }
+  he = hipMemcpy(e->d_occ, nocc, sizeof nocc, hipMemcpyHostToDevice);
+  if (he != hipSuccess) {
+    hipFree(nbuf);
+    return e->hip_fail(he, "rl_resize: publish occupancy");
+  }
+  // nothing below can fail
+  hipFree(e->table);
+  e->table = nbuf;
+  e->tab = nt;
+  e->table_slots = off;
+  for (int u = 0; u < 4; ++u) e->cfg.log2_slots[u] = lg4[u];
+  memcpy(e->occ, nocc, sizeof nocc);
+  e->st.live_keys = e->live_total();
+  return 0;
+}
+
 // ---- Peek / forget ------------------------------------------------------------------------
 // What every form checks first: the call's place among the batches, the arguments' shape and
 // the engine's capacities (blob_bytes only where the engine stages the blob).

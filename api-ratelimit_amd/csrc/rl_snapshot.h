@@ -39,5 +39,9 @@ void launch_snap_export(hipStream_t st, const TableDesc& tab, uint64_t n_slots, 
 // Import n records (device memory), then check the chunk for duplicate identities.
 void launch_snap_import(hipStream_t st, const TableDesc& tab, const Slot* recs, uint32_t n, const SnapGens& gens,
                         SnapCtl* ctl);
+// rl_resize: move every live slot of src (n_slots slots) into dst, a zeroed table of another
+// geometry; counts per (region, class) in ctl->cnt, SNAP_ERR_FULL / _DUP / _GEN in ctl->err.
+void launch_rehash(hipStream_t st, const TableDesc& src, uint64_t n_slots, const SnapGens& gens, const TableDesc& dst,
+                   SnapCtl* ctl);
 
 }  // namespace rlhip

@@ -6,6 +6,8 @@
 //   k_snap_import  one lane per record: claim a slot under the new geometry, write the state
 //   k_snap_verify  one lane per record, after the import of the same chunk: the identity
 //                  occurs exactly once on its probe chain (duplicates inside one chunk)
+//   k_rehash       rl_resize: export's read side and import's claim side in one
+//                  pass, old table -> new table
 #include <hip/hip_runtime.h>
 
 #include "rl_decide.h"
@@ -210,7 +212,91 @@ __global__ __launch_bounds__(256) void k_snap_verify(const TableDesc tab, const 
   if (found > 1u) atomicOr(&ctl->err, SNAP_ERR_DUP);
 }
 
+// Rehash (rl_resize): one pass from the old table straight into the new one, no record buffer in
+// between. Source side as k_snap_export: a block takes tiles of TILE consecutive old slots, every
+// lane reads PER slots with two 16-B loads each, all issued before the first use, and a slot is
+// live by gen_class against its region's newest generation (lag regions keep gen - 2). Destination
+// side as k_snap_import: the slot's place under the new geometry is slot_first of its key; a lane
+// reads the first probe slot of each of its live slots ahead — up to PER random loads in flight
+// together — and only then claims them one after another (table_claim_pre), so the random accesses
+// overlap instead of chaining; then it writes key and state. A read-ahead may predate a claim of
+// that slot (by another lane, or by this lane's earlier claim): table_claim_pre's CAS then fails
+// and the slot is examined again with the word the CAS returned. The new table was zeroed and is
+// below its load limit (rl_resize checks the mirror first), so a free slot exists in every region;
+// a failed claim is SNAP_ERR_FULL. The source is a table, so identities are unique: finding one
+// already in the new table is SNAP_ERR_DUP, and no k_snap_verify pass is needed — two lanes can
+// only both claim a slot for the same identity, and there are no two such lanes. Per (region,
+// class) counts of the slots moved are summed in LDS and added once per tile and non-zero word.
+// No lane waits for another block: the tile loop is bounded by the old slot count, the probe by
+// the new region's size.
+__global__ __launch_bounds__(NT) void k_rehash(const TableDesc src, const uint64_t n_slots, const SnapGens gens,
+                                                const TableDesc dst, SnapCtl* ctl) {
+  __shared__ uint32_t sh_cls[SNAP_CLASSES];
+  const uint32_t tid = threadIdx.x;
+  const uint64_t n_tiles = (n_slots + TILE - 1) / TILE;
+  for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    if (tid < (uint32_t)SNAP_CLASSES) sh_cls[tid] = 0u;
+    __syncthreads();
+    const uint64_t i0 = tile * TILE + tid;
+    uint4 a[PER], b[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const uint64_t i = i0 + (uint64_t)k * NT;
+      a[k] = make_uint4(0u, 0u, 0u, 0u);
+      b[k] = a[k];
+      if (i < n_slots) {
+        const uint4* p = reinterpret_cast<const uint4*>(src.slots + i);
+        a[k] = p[0];
+        b[k] = p[1];
+      }
+    }
+    uint32_t cls[PER];  // region * 2 + class; SNAP_CLASSES = not live
+    uint64_t key[PER];
+    SlotView pre[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const uint64_t i = i0 + (uint64_t)k * NT;
+      const uint32_t r = region_of_slot(src, i);
+      const uint32_t c = i < n_slots ? gen_class(a[k].x, gen_of_region(gens, r), lazy_region(src.lag, r)) : 2u;
+      key[k] = (uint64_t)a[k].z | ((uint64_t)a[k].w << 32);
+      cls[k] = c < 2u ? r * 2u + c : (uint32_t)SNAP_CLASSES;
+      if (c < 2u && key_region(key[k]) != r) {  // a slot outside its key's region: never written by this engine
+        atomicOr(&ctl->err, SNAP_ERR_GEN);
+        cls[k] = (uint32_t)SNAP_CLASSES;
+      }
+      // a lane without a live slot reads the table's first slot: no load behind a branch
+      pre[k] = load_slot(cls[k] < (uint32_t)SNAP_CLASSES ? slot_first(dst, key[k]) : dst.slots);
+    }
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      if (cls[k] >= (uint32_t)SNAP_CLASSES) continue;
+      Slot* slot = nullptr;
+      bool existed = false;
+      KeyState ks{0, 0, 0, 0};
+      if (!table_claim_pre(dst, key[k], a[k].y, a[k].x, pre[k], slot, existed, ks)) {
+        atomicOr(&ctl->err, SNAP_ERR_FULL);
+      } else if (existed) {
+        atomicOr(&ctl->err, SNAP_ERR_DUP);
+      } else {
+        slot->key = key[k];
+        write_state(slot, KeyState{b[k].x, b[k].y, b[k].z, b[k].w});
+        atomicAdd(&sh_cls[cls[k]], 1u);
+      }
+    }
+    __syncthreads();
+    if (tid < (uint32_t)SNAP_CLASSES && sh_cls[tid]) atomicAdd(&ctl->cnt[tid][0], sh_cls[tid]);
+    __syncthreads();  // sh_cls is cleared by the next tile
+  }
+}
+
 }  // namespace snap
+
+void launch_rehash(hipStream_t st, const TableDesc& src, uint64_t n_slots, const SnapGens& gens, const TableDesc& dst,
+                   SnapCtl* ctl) {
+  const uint64_t tiles = (n_slots + snap::TILE - 1) / snap::TILE;
+  const uint32_t grid = (uint32_t)(tiles < 1024 ? (tiles ? tiles : 1) : 1024);
+  hipLaunchKernelGGL(snap::k_rehash, dim3(grid), dim3(snap::NT), 0, st, src, n_slots, gens, dst, ctl);
+}
 
 void launch_snap_export(hipStream_t st, const TableDesc& tab, uint64_t n_slots, const SnapGens& gens, Slot* out,
                         uint64_t cap, SnapCtl* ctl) {

@@ -267,6 +267,7 @@ ABI = [
     ("rl_peek", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
     ("rl_peek_device", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
     ("rl_forget", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
+    ("rl_resize", [C.c_void_p, C.POINTER(C.c_uint32)], C.c_int),
 ]
 
 # multi-GPU router record sizes (include/rl_hip.h RL_ROUTE_*)
@@ -655,6 +656,14 @@ class Engine:
         o = RlOccupancy()
         self._check(self.lib.rl_get_occupancy(self.h, C.byref(o)), "rl_get_occupancy")
         return {k: list(getattr(o, k)) for k in ("gen", "live", "limit", "slots")}
+
+    def resize(self, log2_slots):
+        """rl_resize: move the live slots into a table of log2_slots[u] slots per window
+        generation for home unit u (0 keeps that unit's size), on the device. Needs nothing in
+        flight; a refusal (RedisError with the RL_E* code) leaves the engine exactly as it was."""
+        if len(log2_slots) != 4:
+            raise ValueError("log2_slots: four entries (SECOND, MINUTE, HOUR, DAY homes)")
+        self._check(self.lib.rl_resize(self.h, (C.c_uint32 * 4)(*log2_slots)), "rl_resize")
 
     def submit_device_async(self, n_desc: int, n_req: int, blob_bytes: int, ptrs, out_ptr: int, thr_ptr: int):
         s = RlBatch()
@@ -1179,6 +1188,10 @@ class HipRateLimitCache:
     def load(self, path):
         """Restore the counters from a snapshot file (Engine.load)."""
         return self.engine.load(path)
+
+    def resize(self, log2_slots):
+        """Resize the counter table on the device (Engine.resize); 0 keeps a unit's size."""
+        return self.engine.resize(log2_slots)
 
     def do_limit_batch(self, calls) -> list:
         reqs = []

@@ -527,7 +527,10 @@ void rl_router_destroy(rl_router* r);
 int rl_reset(rl_engine* e);
 
 int rl_get_stats(rl_engine* e, rl_engine_stats* s);
-/* Table occupancy (synchronises the engine's stream; not while a batch is in flight). */
+/* Table occupancy, from the engine's host mirror: no device call and no synchronisation. The
+ * mirror is advanced by rl_wait / rl_wait_into as each batch completes, so the figures are those
+ * after the last completed batch; batches still in flight are not in them yet. Legal at any point
+ * on the engine's thread (a batcher reads it between rl_waits). */
 int rl_get_occupancy(rl_engine* e, rl_occupancy* o);
 
 /* Per-kernel timing with HIP events on the engine stream (off by default). When on, each
@@ -613,6 +616,45 @@ int rl_snapshot_end(rl_engine* e);
 int rl_restore_begin(rl_engine* e, const rl_snapshot_header* hdr);
 int rl_restore_put(rl_engine* e, const void* host_recs, uint32_t n);
 int rl_restore_end(rl_engine* e);
+
+/* ---- Resize ---------------------------------------------------------------
+ * Resize the counter table in place: log2_slots[u] slots per window generation for home unit u
+ * (0 = keep that unit's size). Every live slot ("What is live" above) keeps its claim word, key,
+ * counters, expiry and local-cache deadline; only its place changes. One device pass reads the
+ * old table and claims each live slot's place in the new one (no host copy, no record buffer);
+ * the call returns after a stream synchronise, and that pass plus the new table's clearing is
+ * the whole pause. The hot set and the candidate stash hold key prefixes, not slots, and are
+ * kept: the next batch runs as if nothing had happened. An open snapshot is a separate device
+ * copy and does not block the call; rl_snapshot_next keeps draining the records of its begin.
+ *
+ * Refused before anything changes, the engine exactly as it was:
+ *   RL_ESTATE  a batch is in flight (call rl_wait until none is: a resize while batches are in
+ *              flight is out of scope), or a restore is open;
+ *   RL_EINVAL  a non-zero log2 outside 4..31;
+ *   RL_ENOSPC  a region's mirrored live + prev exceeds its new load limit,
+ *              2^log2 * max_load_permille / 1000. The mirror never under-counts but may
+ *              over-count, so a shrink to within a few slots of the true live count can be
+ *              refused although it would fit: the check is conservative, never unsafe;
+ *   RL_EHIP    the new table cannot be allocated. Old and new table coexist during the call:
+ *              peak device memory is 32 B * (sum of old slots + sum of new slots), i.e. three
+ *              times the old table for a doubling of every unit.
+ * After the checks a failure of the pass itself — a device error word, a count above the
+ * mirror's (RL_EDEVICE), a HIP error (RL_EHIP) — frees the new table; the old one was only read
+ * and stays in service. Only on success the tables are swapped, the old one is freed, the load
+ * limits follow the new sizes, the occupancy's live / prev become the exact counts of the pass
+ * (gen is unchanged) and rl_engine_stats.live_keys follows; inserted_keys is cumulative and does
+ * not change. Legal on a router's engine between steps.
+ *
+ * Auto-grow is the batcher's, not the engine's (rl_cache.hpp HipSettings::autogrow_permille,
+ * HIP_TABLE_AUTOGROW): after each completed batch it reads rl_get_occupancy,
+ * and when either parity region of a home unit holds more than slots * autogrow_permille / 1000
+ * live slots and the unit is below its maximum (HIP_TABLE_MAX_SLOTS) it completes the batches in
+ * flight and calls rl_resize with that unit's log2 + 1 — before a batch is refused with
+ * RL_ENOSPC whenever the watermark is below max_load_permille. A single batch that jumps from
+ * under the watermark to over the limit is still refused, and the growth follows it.
+ * Out of scope: the routed batcher (every rank would have to resize between the same two
+ * steps), and resizing while batches are in flight. */
+int rl_resize(rl_engine* e, const uint32_t log2_slots[4]);
 
 /* ---- Peek / forget: read and clear counters by key -----------------------
  * What an operator does to the Redis backend with GET / TTL domain_key_value_<window> and DEL,
