@@ -215,6 +215,91 @@ def test_repack_when_a_group_is_not_one_key_string():
     r.close()
 
 
+def test_wrap_and_prefix_range_inside_combined_records():
+    """A hot key's counter is left at 2^32 - 50 by one huge hits_addend (past the combining range:
+    a repack), and the next step's small hits wrap inside the combined records: each descriptor's
+    reply is the group's reply minus the group's sum plus its own prefix, in uint32.
+    Then the width of a combined descriptor's in-record prefix (PERM_HOT_PRE_BITS = 22). The prefix
+    runs inside one pack block of 1024 descriptors and a combined h is at most 4095, so a block's
+    sum stays below 2^22 by construction; sums over blocks travel in the per-block offsets. So an
+    origin whose hits for one group sum to 2^22 - 1, and to 2^22, over two blocks (the first one
+    full: 1024 x 4095, the largest prefix there is) combines both times, sending one record; the
+    guard of the field is h itself: one descriptor of h = 4096 is a repack."""
+    G, per, t0 = 2, 2000, 1_700_000_000
+    steps = skew_batches(G, 16, per, seed=73, t0=t0)
+    b = steps[0][0]
+    hot = {b.prefix(i): int(b.rule[i]) for i in range(b.n_desc) if b.prefix(i).startswith(b"cmb_hot_")}
+    # a hot key whose counter outlives the step's second and whose limit holds a step's largest h
+    pfx, rule = next((p, r) for p, r in sorted(hot.items()) if RULES[r][1] != hiprl.SECOND and RULES[r][0] >= 8)
+    name = pfx.decode().split("_")[2]
+    L, unit = RULES[rule][:2]
+
+    def x_only(hs, t):
+        return hiprl.build_batch([("cmb", [[("hot", name)]], [rule], h, t) for h in hs])
+
+    def x_desc(b):
+        return [i for i in range(b.n_desc) if b.prefix(i) == pfx]
+
+    def x_hits(b):
+        return sum(max(1, int(b.hits[b.req_of[i]])) for i in x_desc(b))
+
+    def count(t):
+        return max(0, o.counter(oracle.cache_key(pfx, unit, t), t))
+
+    r = hiprl.Router(engines(G, 3 * per * G), max_desc=3 * per)
+    o = new_oracle()
+
+    def step(batches, ctx):
+        """One step against the oracle; returns the oracle's statuses per origin and the changes
+        of (repacks, combined_steps)."""
+        s0 = r.stats()
+        bf = Bufs(batches)
+        torch.cuda.synchronize()
+        r.step(*bf.args())
+        est, ethr = o.submit(routing.concat_batches(batches))
+        want, d0, r0 = [], 0, 0
+        for g, (b, (st, thr)) in enumerate(zip(batches, bf.results())):
+            streams.assert_same(est[d0:d0 + b.n_desc], ethr[r0:r0 + b.n_req], st, thr, f"{ctx} origin={g}")
+            want.append(est[d0:d0 + b.n_desc])
+            d0 += b.n_desc
+            r0 += b.n_req
+        s1 = r.stats()
+        return want, (s1["repacks"] - s0["repacks"], s1["combined_steps"] - s0["combined_steps"]), s1
+
+    run_steps(r, steps[:11], o, "sync", "forming the hot set")
+    assert r.stats()["combined_steps"] >= 2, r.stats()
+    # step 11: the counter to 2^32 - 50 with one huge hits_addend behind origin 0's usual batch
+    t = t0 + 11
+    H = 2 ** 32 - 50 - count(t) - sum(x_hits(b) for b in steps[11])
+    assert H > 4095
+    _, d, s = step([routing.concat_batches([steps[11][0], x_only([H], t)]), steps[11][1]], "huge hits_addend")
+    assert d == (1, 0), s  # the key is in origin 0's hot set (only there is its h checked), and the step is repacked
+    assert count(t) == 2 ** 32 - 50
+    # step 12: small hits, combined, wrap inside the combined records
+    t = t0 + 12
+    assert sum(x_hits(b) for b in steps[12]) >= 100 and all(int(b.hits.max()) <= 8 for b in steps[12])
+    want, d, s = step(steps[12], "wrap inside combined records")
+    assert d == (0, 1) and s["combined"] > 0, s
+    c = count(t)
+    assert 2 ** 32 <= c < 2 ** 32 + 16000  # the proof of the wrap: the oracle's own counter passed 2^32
+    codes = np.concatenate([w[x_desc(b)]["code_flags"] for w, b in zip(want, steps[12])])
+    first_ok = np.nonzero((codes & 0xFF == hiprl.CODE_OK) & ((codes >> 8) & hiprl.FLAG_SHADOW == 0))[0]
+    # ... and its decisions show it: OVER_LIMIT up to the wrap, OK right behind it (h <= 8 <= L,
+    # so a reply lands in 0..L)
+    assert L >= 8, (pfx, rule, L)
+    assert len(first_ok) and first_ok[0] > 0, codes
+    # step 13: origin 0's hits for the group sum to 2^22 - 1, the first pack block full of 4095s
+    want, d, s = step([x_only([4095] * 1024 + [1023], t0 + 13), steps[13][1]], "sum 2^22 - 1")
+    assert d == (0, 1) and sum(s["sent"]) == 1, s
+    # step 14: one descriptor past the largest combined h
+    want, d, s = step([x_only([8] * 64 + [4096], t0 + 14), steps[14][1]], "h = 4096")
+    assert d == (1, 0) and sum(s["sent"]) == 65, s
+    # step 15: the sum one higher than in step 13
+    want, d, s = step([x_only([4095] * 1024 + [1024], t0 + 15), steps[15][1]], "sum 2^22")
+    assert d == (0, 1) and sum(s["sent"]) == 1, s
+    r.close()
+
+
 def test_repack_over_many_pack_blocks():
     """A repack over many pack blocks: a batch of ~75k descriptors (74 pack blocks of 1024, the
     repack's look-back over all of them) whose hot descriptors carry two request times, after the
