@@ -77,6 +77,8 @@ void launch_v4_group(hipStream_t st, const rl_batch& b, const DevRule* rules, ui
                      const uint16_t* tstart);
 void launch_peek(hipStream_t, const rl_batch&, const DevRule*, uint32_t, uint64_t, const TableDesc&, rl_peek_reply*,
                  bool forget);
+void launch_rule_stats(hipStream_t, const rl_batch&, const rl_status*, uint32_t, rl_rule_stat*, const EngineCtl*, int,
+                       uint32_t);
 }  // namespace rlhip
 
 using namespace rlhip;
@@ -85,12 +87,12 @@ namespace {
 
 enum KernelId {
   KT_FINGERPRINT, KT_HISTOGRAM, KT_HIST_SCAN, KT_SORT_PASS, KT_SCAN, KT_LEADER, KT_DECIDE, KT_FALLBACK, KT_MEMSET,
-  KT_CAND, KT_V4_HIST, KT_V4_SCAN, KT_V4_PLACE, KT_V4_GROUP, KT_RESOLVE, KT_COUNT
+  KT_CAND, KT_V4_HIST, KT_V4_SCAN, KT_V4_PLACE, KT_V4_GROUP, KT_RESOLVE, KT_RULE_STATS, KT_COUNT
 };
 const char* const kKernelNames[KT_COUNT] = {"k_fingerprint", "k_histogram", "k_hist_scan", "k_sort_pass", "k_scan",
                                             "k_leader",      "k_decide",    "fallback",    "memset",      "k_cand_state",
                                             "k4_hist",       "k4_scan",     "k4_place",    "k4_group",
-                                            "k_resolve"};
+                                            "k_resolve",     "k_rule_stats"};
 
 enum Mode { MODE_LSD = 1, MODE_LSD_FULL = 2, MODE_V4 = 4 };
 
@@ -137,6 +139,20 @@ struct rl_engine {
   DevRule* d_rules = nullptr;
   uint32_t n_rules = 0, rules_cap = 0;
   std::vector<DevRule> h_rules;      // what d_rules[0, n_rules) holds
+
+  // rule stats (rl_hip.h "Rule stats"): one row per rule id d_rules has room for, allocated at
+  // first use and regrown with d_rules, contents kept
+  rl_rule_stat* d_rstats = nullptr;
+  uint32_t rstats_cap = 0;
+  int rs_variant = 0;                // 0: sums of low rule ids in LDS; 1: global adds only (RL_DIAG_RULE_STATS_VARIANT)
+  uint32_t rs_blocks = 256;          // k_rule_stats' persistent grid (RL_DIAG_RULE_STATS_BLOCKS)
+  int rstats_ensure();
+  int count_batch(const rl_batch& b, const rl_status* out, const EngineCtl* ctl);
+  bool counts(const rl_batch& b) const { return (cfg.flags & RL_CFG_RULE_STATS) && !b.reserved && b.n_desc; }
+  // the control block run_pipeline gives the batch it is about to run in `mode`
+  const EngineCtl* batch_ctl(int mode) const {
+    return mode == MODE_V4 ? v4_ctl[sub_seq % 3] : reinterpret_cast<const EngineCtl*>(zero_block);
+  }
 
   // host staging (rl_submit): per host slot one pinned input region with the device layout,
   // its device twin, device outputs and pinned outputs
@@ -301,6 +317,7 @@ struct rl_engine {
     rl_status* user_out = nullptr; // host batch: rl_wait copies here (may be null)
     uint32_t* user_thr = nullptr;
     bool poll = false;             // completion = k4_group's done word behind h_ctl (no event)
+    bool count = false;            // RL_CFG_RULE_STATS: k_rule_stats runs behind the batch's pipeline
   };
   Flight fl[HSLOTS];
   // A device v4 batch completes on the word k4_group's last block writes behind the slot's pinned
@@ -374,6 +391,18 @@ struct rl_engine {
     f();
     hipEventRecord(b, stream);
     marks.push_back({kid, a, b});
+  }
+
+  // the finished event pairs into the per-kernel totals (the stream is synchronised)
+  void fold_marks() {
+    for (auto& m : marks) {
+      float ms = 0;
+      hipEventElapsedTime(&ms, m.a, m.b);
+      kt_ms[m.kid] += ms;
+      kt_n[m.kid] += 1;
+    }
+    marks.clear();
+    ev_used = 0;
   }
 
   // Layout of the LSD per-batch zero block for n descriptors.
@@ -687,6 +716,42 @@ void rl_engine::update_hot(const HotCand* cand, uint32_t n_cand) {
   }
 }
 
+// The rule-stat rows: one per rule id of d_rules' allocation. Growing keeps the contents; the
+// copy is ordered behind every k_rule_stats queued on the stream.
+int rl_engine::rstats_ensure() {
+  if (!d_rules) {
+    int rc = rl_load_rules(this, nullptr, 0);
+    if (rc) return rc;
+  }
+  if (d_rstats && rstats_cap >= rules_cap) return 0;
+  rl_rule_stat* nt = nullptr;
+  hipError_t he = hipMalloc(&nt, (size_t)rules_cap * sizeof(rl_rule_stat));
+  if (he != hipSuccess) {
+    (void)hipGetLastError();
+    return hip_fail(he, "hipMalloc(rule stats)");
+  }
+  he = hipMemsetAsync(nt, 0, (size_t)rules_cap * sizeof(rl_rule_stat), stream);
+  if (he == hipSuccess && d_rstats)
+    he = hipMemcpyAsync(nt, d_rstats, (size_t)rstats_cap * sizeof(rl_rule_stat), hipMemcpyDeviceToDevice, stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(stream);
+  if (he != hipSuccess) {
+    hipFree(nt);
+    return hip_fail(he, "rule stats allocation");
+  }
+  hipFree(d_rstats);
+  d_rstats = nt;
+  rstats_cap = rules_cap;
+  return 0;
+}
+
+int rl_engine::count_batch(const rl_batch& b, const rl_status* out, const EngineCtl* ctl) {
+  int rc = rstats_ensure();
+  if (rc) return rc;
+  timed(KT_RULE_STATS, [&] { launch_rule_stats(stream, b, out, n_rules, d_rstats, ctl, rs_variant, rs_blocks); });
+  const hipError_t he = hipGetLastError();
+  return he == hipSuccess ? 0 : hip_fail(he, "k_rule_stats launch");
+}
+
 int rl_engine::enqueue_d2h(const Flight& f, hipStream_t s) {
   hipError_t e;
   const Stage& g = stage[f.slot];
@@ -729,6 +794,9 @@ int rl_engine::settle(Flight& f) {
     st.inserted_keys += h_ctl->n_inserted;
     int rc = run_pipeline(f.b, f.out, f.thr, MODE_LSD, nullptr, true);
     if (rc) return rc;
+    // (the first attempt's k_rule_stats saw its error word and counted nothing; this one sees
+    // the rerun's: a rerun that asks for a re-sort is counted behind that)
+    if (f.count && (rc = count_batch(f.b, f.out, batch_ctl(MODE_LSD))) != 0) return rc;
     if (f.reply) launch_route_reply(stream, f.b.n_desc, f.out, f.thr, f.reply);
     if (f.host && (rc = enqueue_d2h(f, stream)) != 0) return rc;
     e = hipStreamSynchronize(stream);
@@ -741,6 +809,7 @@ int rl_engine::settle(Flight& f) {
     ++st.resorts;
     int rc = run_pipeline(f.b, f.out, f.thr, MODE_LSD_FULL, nullptr, true);
     if (rc) return rc;
+    if (f.count && (rc = count_batch(f.b, f.out, batch_ctl(MODE_LSD_FULL))) != 0) return rc;
     if (f.reply) launch_route_reply(stream, f.b.n_desc, f.out, f.thr, f.reply);
     if (f.host && (rc = enqueue_d2h(f, stream)) != 0) return rc;
     e = hipStreamSynchronize(stream);
@@ -781,14 +850,7 @@ int rl_engine::finish(rl_status* out_into, uint32_t* thr_into, bool into) {
   if (timing) {
     hipError_t e = hipStreamSynchronize(stream);  // the next batch's marks too
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-    for (auto& m : marks) {
-      float ms = 0;
-      hipEventElapsedTime(&ms, m.a, m.b);
-      kt_ms[m.kid] += ms;
-      kt_n[m.kid] += 1;
-    }
-    marks.clear();
-    ev_used = 0;
+    fold_marks();
   }
   if (errs & ERR_BAD_INPUT)
     return fail(RL_EINVAL, "batch references an unknown rule id or request index, or malformed prefix offsets / "
@@ -866,6 +928,13 @@ int rl_engine::submit_common(const rl_batch& d, rl_status* out, uint32_t* thr, R
   if (rc) return rc;
   if (reply) launch_route_reply(stream, d.n_desc, out, thr, reply);
   Flight f;
+  // Rule stats from the final statuses, right behind the pipeline: the batch's control block is
+  // complete there (every kernel that writes its error word is ahead on the stream, k4_hist
+  // through the front stream's join) and is cleared only by the next batch's pipeline, behind
+  // this launch (k4_group clears the block of the batch two after its own; the LSD block is
+  // zeroed at the start of the next LSD run).
+  f.count = counts(d);
+  if (f.count && (rc = count_batch(d, out, batch_ctl(default_mode()))) != 0) return rc;
   f.b = d;
   f.out = out;
   f.thr = thr;
@@ -889,7 +958,9 @@ int rl_engine::submit_common(const rl_batch& d, rl_status* out, uint32_t* thr, R
     // outputs stay in device memory; the host summary was written with a system-scope
     // release by k4_group (or copied by the LSD path's own D2H copy, ordered before this)
     const bool dev_only = default_mode() == MODE_V4 && !reply && d.n_desc;
-    if (dev_only && !timing) {
+    // (a counted batch completes on an event behind k_rule_stats, which still reads its arrays
+    // after k4_group's done word)
+    if (dev_only && !timing && !f.count) {
       f.poll = true;  // k4_group writes the done word (cleared at this submit's start)
       e = hipSuccess;
     } else {
@@ -973,6 +1044,9 @@ int rl_create(const rl_config* cfg_in, rl_engine** out) {
   if (c.sort_bits == 0) c.sort_bits = 48;
   if (c.sort_bits % 8 || c.sort_bits < 8 || c.sort_bits > 64) { delete e; return RL_EINVAL; }
   e->npasses = (int)c.sort_bits / 8;
+  if (const char* v = getenv("RL_DIAG_RULE_STATS_VARIANT")) e->rs_variant = atoi(v) == 1 ? 1 : 0;  // diagnostics (A/B)
+  if (const char* v = getenv("RL_DIAG_RULE_STATS_BLOCKS"))
+    e->rs_blocks = std::min<uint32_t>(std::max<uint32_t>((uint32_t)strtoul(v, nullptr, 10), 1u), 1024u);
   e->lo_bit = 64 - (int)c.sort_bits;
   hipError_t he = hipSetDevice(c.device);
   if (he != hipSuccess) {
@@ -1151,7 +1225,7 @@ void rl_destroy(rl_engine* e) {
   for (void* p : {(void*)e->v4_hoff, (void*)e->v4_dfr, (void*)e->v4_hb,
                   e->v4_scratch, (void*)e->d_poison, (void*)e->d_tree_nodes,
                   (void*)e->d_tree_slots, (void*)e->d_tree_names, (void*)e->d_tree_fnodes, (void*)e->d_tree_fslots, (void*)e->d_res, (void*)e->d_res_flags, (void*)e->table, (void*)e->d_occ,
-                  (void*)e->d_rules, (void*)e->keys_orig, (void*)e->keys_a, (void*)e->keys_b, (void*)e->vals_a,
+                  (void*)e->d_rules, (void*)e->d_rstats, (void*)e->keys_orig, (void*)e->keys_a, (void*)e->keys_b, (void*)e->vals_a,
                   (void*)e->vals_b, (void*)e->recs, (void*)e->srec, (void*)e->seg, (void*)e->offs,
                   (void*)e->hist_part, (void*)e->fp_part, (void*)e->fp_part2, (void*)e->tile_heads,
                   (void*)e->zero_block, (void*)e->d_cand, (void*)e->r_tmp, (void*)e->r_own, (void*)e->r_bcnt,
@@ -1213,6 +1287,11 @@ int rl_load_rules(rl_engine* e, const rl_rule* rules, uint32_t n) {
       return e->hip_fail(he, "hipMalloc(rules)");
     }
     e->rules_cap = cap;
+    // the stat rows follow the rule table's room (nothing is in flight here)
+    if (e->d_rstats) {
+      int rc = e->rstats_ensure();
+      if (rc) return rc;
+    }
   }
   if (n > first) {
     hipError_t he = hipMemcpy(e->d_rules + first, h.data() + first, (size_t)(n - first) * sizeof(DevRule),
@@ -2159,6 +2238,38 @@ int rl_peek_device(rl_engine* e, const rl_batch* b, rl_peek_reply* d_out) {
   return 0;
 }
 
+// ---- Rule stats ---------------------------------------------------------------------------
+int rl_rule_stats_add_device(rl_engine* e, const rl_batch* b, const rl_status* d_out) {
+  if (!e || !b) return RL_EINVAL;
+  if (b->reserved) return e->fail(RL_EINVAL, "rl_batch.reserved must be 0");
+  if (b->n_desc > (1u << 30)) return e->fail(RL_EINVAL, "rl_rule_stats_add_device: more than 2^30 descriptors");
+  if (b->n_desc && (!b->rule_id || !b->req_of || !b->hits_addend || !d_out))
+    return e->fail(RL_EINVAL, "rl_rule_stats_add_device: null rule_id / req_of / hits_addend / status array");
+  if (!b->n_desc) return 0;
+  return e->count_batch(*b, d_out, nullptr);
+}
+
+int rl_rule_stats_read(rl_engine* e, uint32_t first_rule, uint32_t n, rl_rule_stat* out, uint32_t flags) {
+  if (!e) return RL_EINVAL;
+  if (e->n_fl) return e->fail(RL_ESTATE, "rl_rule_stats_read while a batch is in flight (call rl_wait)");
+  if (e->restoring) return e->fail(RL_ESTATE, "rl_rule_stats_read between rl_restore_begin and rl_restore_end");
+  if (flags & ~(uint32_t)RL_RULE_STATS_CLEAR) return e->fail(RL_EINVAL, "unknown rl_rule_stats_read flags 0x%x", flags);
+  if ((uint64_t)first_rule + n > e->n_rules)
+    return e->fail(RL_EINVAL, "rl_rule_stats_read: rules [%u, %llu) of %u loaded", first_rule,
+                   (unsigned long long)first_rule + n, e->n_rules);
+  if (n && !out) return e->fail(RL_EINVAL, "rl_rule_stats_read: null output array");
+  int rc = e->rstats_ensure();
+  if (rc) return rc;
+  // behind every k_rule_stats queued on the engine stream, the explicit calls' included
+  const size_t bytes = (size_t)n * sizeof(rl_rule_stat);
+  hipError_t he = hipSuccess;
+  if (n) he = hipMemcpyAsync(out, e->d_rstats + first_rule, bytes, hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess && n && (flags & RL_RULE_STATS_CLEAR))
+    he = hipMemsetAsync(e->d_rstats + first_rule, 0, bytes, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  return he == hipSuccess ? 0 : e->hip_fail(he, "rl_rule_stats_read");
+}
+
 int rl_set_timing(rl_engine* e, int on) {
   if (!e) return RL_EINVAL;
   if (e->n_fl) return e->fail(RL_ESTATE, "rl_set_timing while a batch is in flight");
@@ -2170,6 +2281,12 @@ int rl_set_timing(rl_engine* e, int on) {
 int rl_kernel_times(rl_engine* e, const char** names, double* total_ms, uint64_t* launches, uint32_t cap,
                     uint32_t* n_out) {
   if (!e) return RL_EINVAL;
+  if (e->timing && !e->n_fl && !e->marks.empty()) {
+    // kernels timed outside a batch (rl_rule_stats_add_device, rl_resolve_device): no rl_wait folds them
+    const hipError_t he = hipStreamSynchronize(e->stream);
+    if (he != hipSuccess) return e->hip_fail(he, "hipStreamSynchronize");
+    e->fold_marks();
+  }
   uint32_t n = 0;
   for (int k = 0; k < KT_COUNT && n < cap; ++k, ++n) {
     if (names) names[n] = kKernelNames[k];

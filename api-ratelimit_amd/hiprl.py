@@ -41,6 +41,7 @@ STATUS_DTYPE = np.dtype([("code_flags", "<u4"), ("limit_remaining", "<u4"), ("re
 
 PIPELINE_FLAGS = {"v4": 0, "lsd": 1}  # rl_config.flags (RL_CFG_LSD_ONLY)
 CFG_LAG_WINDOW = 2  # RL_CFG_LAG_WINDOW: SECOND key strings findable 3 s behind (routers' engines)
+CFG_RULE_STATS = 4  # RL_CFG_RULE_STATS: every completed batch is added to the per-rule stat counters
 ABI_VERSION = 7
 
 
@@ -116,6 +117,12 @@ RAW_DTYPE = np.dtype([("after", "<u4"), ("flags", "<u4")])
 # ---- peek / forget (rl_hip.h "Peek / forget") ----
 PEEK_FOUND, PEEK_LOCAL_CACHED, PEEK_NIL, PEEK_PER_SECOND, PEEK_BAD = 1, 2, 4, 8, 16  # rl_peek_reply.flags
 PEEK_DTYPE = np.dtype([("count", "<u4"), ("ttl_s", "<u4"), ("cached_s", "<u4"), ("flags", "<u4")])
+
+
+# ---- rule stats (rl_hip.h "Rule stats") ----
+RULE_STATS_CLEAR = 1  # RL_RULE_STATS_CLEAR
+RULE_STAT_FIELDS = ("total_hits", "over_limit", "near_limit", "over_limit_with_local_cache", "shadow_mode")
+RULE_STAT_DTYPE = np.dtype([(f, "<u8") for f in RULE_STAT_FIELDS] + [("reserved", "<u8", (3,))])  # rl_rule_stat, 64 B
 
 
 # ---- snapshot / restore (rl_hip.h "Snapshot / restore") ----
@@ -268,6 +275,8 @@ ABI = [
     ("rl_peek_device", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
     ("rl_forget", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
     ("rl_resize", [C.c_void_p, C.POINTER(C.c_uint32)], C.c_int),
+    ("rl_rule_stats_add_device", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
+    ("rl_rule_stats_read", [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32], C.c_int),
 ]
 
 # multi-GPU router record sizes (include/rl_hip.h RL_ROUTE_*)
@@ -469,7 +478,8 @@ class Engine:
                  local_cache: bool = False, per_second_split: bool = False, max_batch_desc: int = 1 << 16,
                  max_batch_req: Optional[int] = None, max_blob_bytes: Optional[int] = None, sort_bits: int = 48,
                  hash_seed: int = 0x5EE7AB1E5EED, lib_path: Optional[os.PathLike] = None, lsd_only: bool = False,
-                 pipeline: str = "v4", max_load_permille: int = 0, lag_window: bool = False):
+                 pipeline: str = "v4", max_load_permille: int = 0, lag_window: bool = False,
+                 rule_stats: bool = False):
         """pipeline: "v4" (default: tile-sorted records, hot keys decided in place, MSD buckets
         gathered and grouped in LDS) or "lsd" (radix-sort pipeline, also v4's fallback).
         lsd_only=True is pipeline="lsd". log2_slots: table slots per window generation for the
@@ -491,7 +501,8 @@ class Engine:
         cfg.max_batch_req = max_batch_req or max_batch_desc
         cfg.max_blob_bytes = max_blob_bytes or max_batch_desc * 64
         cfg.sort_bits = sort_bits
-        cfg.flags = PIPELINE_FLAGS[pipeline] | (CFG_LAG_WINDOW if lag_window else 0)
+        cfg.flags = (PIPELINE_FLAGS[pipeline] | (CFG_LAG_WINDOW if lag_window else 0) |
+                     (CFG_RULE_STATS if rule_stats else 0))
         cfg.hash_seed = hash_seed
         cfg.max_load_permille = max_load_permille
         self.cfg = cfg
@@ -526,6 +537,7 @@ class Engine:
             arr[i].requests_per_unit = r[0]
             arr[i].unit = r[1] | (RULE_SHADOW if len(r) > 2 and r[2] else 0)
         self._check(self.lib.rl_load_rules(self.h, arr, len(rules)), "rl_load_rules")
+        self.n_rules = len(rules)
 
     def submit(self, b: Batch):
         """Host batch -> (status[n_desc] structured array, throttle_ms[n_req]); one batch in flight."""
@@ -746,6 +758,28 @@ class Engine:
         s.n_desc, s.n_req, s.blob_bytes, s.reserved = n_desc, n_req, blob_bytes, 0
         _set_ptrs(s, ptrs)
         self._check(self.lib.rl_peek_device(self.h, C.byref(s), out_ptr), "rl_peek_device")
+
+    # ---- rule stats (rl_hip.h "Rule stats") ----
+    def rule_stats(self, first: int = 0, n: Optional[int] = None, clear: bool = False) -> np.ndarray:
+        """rl_rule_stats_read: the stat counters of rule ids [first, first + n) (RULE_STAT_DTYPE;
+        n=None: up to the last rule loaded through this object), zeroed afterwards with clear.
+        Needs nothing in flight."""
+        if n is None:
+            n = max(0, getattr(self, "n_rules", 0) - first)
+        out = np.zeros(n, RULE_STAT_DTYPE)
+        self._check(self.lib.rl_rule_stats_read(self.h, first, n, _ptr(out) or None, RULE_STATS_CLEAR if clear else 0),
+                    "rl_rule_stats_read")
+        return out
+
+    def rule_stats_add_device(self, n_desc: int, n_req: int, blob_bytes: int, ptrs, out_ptr: int):
+        """rl_rule_stats_add_device: add the statuses at out_ptr (device memory, n_desc rl_status) of
+        an rl_batch of device pointers (ptrs = blob, off, rule, req_of, now, hits; only rule,
+        req_of and hits are read, the others may be 0) to the per-rule counters, asynchronous on
+        the engine stream."""
+        s = RlBatch()
+        s.n_desc, s.n_req, s.blob_bytes, s.reserved = n_desc, n_req, blob_bytes, 0
+        _set_ptrs(s, ptrs)
+        self._check(self.lib.rl_rule_stats_add_device(self.h, C.byref(s), out_ptr), "rl_rule_stats_add_device")
 
     # ---- snapshot / restore (rl_hip.h "Snapshot / restore") ----
     def snapshot_begin(self) -> RlSnapshotHeader:

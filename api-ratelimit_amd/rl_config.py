@@ -135,6 +135,19 @@ class RateLimitConfig:
         nodes, names = self.tree_arrays()
         engine.load_tree(nodes, names)
 
+    def stats(self, engine: "hiprl.Engine", clear: bool = False) -> Dict[str, int]:
+        """The device's per-rule stat counters (rl_rule_stats_read) under the reference's stat
+        names, "<full_key>.total_hits" ... (newRateLimitStats, config_impl.go:64-70) plus
+        ".shadow_mode". Rules that share a full_key — the overrides of one key,
+        config_impl.go:286-296 — are summed. Needs nothing in flight."""
+        rows = engine.rule_stats(0, len(self.rules), clear=clear)
+        out: Dict[str, int] = {}
+        for rule, row in zip(self.rules, rows):
+            for f in hiprl.RULE_STAT_FIELDS:
+                k = rule.full_key + "." + f
+                out[k] = (out.get(k, 0) + int(row[f])) & 0xFFFFFFFFFFFFFFFF
+        return out
+
 
 class ResolveBatch:
     """One rl_resolve_batch: descriptors [(domain, [(key, value)...], override_rule or None)].

@@ -87,10 +87,12 @@ typedef struct rl_config {
 /* rl_config.flags */
 enum {
   RL_CFG_LSD_ONLY = 1u,  /* always use the LSD radix-sort pipeline (default: v4 pipeline, LSD as fallback) */
-  RL_CFG_LAG_WINDOW = 2u /* keep a SECOND key string findable for requests up to 3 s behind the newest time the
+  RL_CFG_LAG_WINDOW = 2u,/* keep a SECOND key string findable for requests up to 3 s behind the newest time the
                             table has seen, at up to twice the SECOND regions' live slots against the same load
                             limit. rl_router_create turns it on for its engines (origins' clocks differ); a lone
                             engine fed in enqueue order does not need it */
+  RL_CFG_RULE_STATS = 4u /* add every completed batch's stat increments to the per-rule counters on the device
+                            ("Rule stats" below) */
 };
 
 /* One rate-limit rule: config.RateLimit.Limit (src/config/config.go:26-32). */
@@ -711,6 +713,62 @@ typedef struct rl_peek_reply { /* 16 B */
 int rl_peek(rl_engine* e, const rl_batch* host_batch, rl_peek_reply* out);
 int rl_peek_device(rl_engine* e, const rl_batch* device_batch, rl_peek_reply* d_out);
 int rl_forget(rl_engine* e, const rl_batch* host_batch, rl_peek_reply* out_or_null);
+
+/* ---- Rule stats: per-rule stat counters summed on the device ---------------
+ * The reference keeps four counters per limit, <FullKey>.total_hits / .over_limit / .near_limit /
+ * .over_limit_with_local_cache (src/config/config_impl.go:64-70), and BaseRateLimiter adds to
+ * them for every descriptor (base_limiter.go:49-51, 77-78, 129-177). An rl_status carries the
+ * increments and a host that reads the statuses adds them up itself; on the device path
+ * (rl_resolve_device -> rl_submit_pipelined) the host reads no status, so the engine keeps one
+ * rl_rule_stat row per rule id in device memory and a kernel adds a batch's increments to it.
+ *
+ * Contribution of descriptor i, with r = rule_id[i]: nothing for RL_NIL_RULE; otherwise
+ * total_hits[r] += max(1, hits_addend[req_of[i]]), and when its status has RL_FLAG_HAS_LIMIT the
+ * other four words as annotated below. Sums are 64-bit and wrap. A rule id at or above the loaded
+ * rule count, or a request index at or above n_req, adds nothing and indexes nothing (only the
+ * explicit call can meet either: a submit refuses such a batch).
+ *
+ * rl_rule_stats_add_device folds the statuses d_out[n_desc] of one device batch into the rows.
+ * It reads rule_id, req_of, hits_addend, n_desc and n_req of the rl_batch (the other arrays may
+ * be NULL; n_desc <= 2^30), is ordered on the engine stream, returns at once and is legal at any
+ * time, batches in flight included. The caller leaves the arrays alone until work it orders
+ * behind it on rl_stream(e) has run, or until the next rl_rule_stats_read. A routed origin calls
+ * it on the statuses rl_route_unpack left in device memory.
+ *
+ * RL_CFG_RULE_STATS makes it automatic: every batch completed through rl_submit,
+ * rl_submit_device or rl_submit_pipelined is folded in exactly once, from its final statuses —
+ * also a batch the device handed to the LSD pipeline, re-sorted, or refused behind a refused one
+ * and ran again. A batch whose rl_wait returns an error counts nothing. (The reference differs
+ * there: it adds TotalHits before the Redis call, base_limiter.go:49-51, so it counts the hits of
+ * a request whose Redis call then fails.) The raw forms (rl_submit_c, RL_ROUTED_RAW) and
+ * rl_submit_routed are not counted at the owner: their decisions are made, or reported, elsewhere.
+ * With the flag set a device batch completes on an event behind the counting kernel, so its
+ * arrays are the caller's again when rl_wait returns, as without the flag.
+ *
+ * rl_rule_stats_read synchronises the engine stream and copies rows [first_rule, first_rule + n)
+ * to host memory; with RL_RULE_STATS_CLEAR it zeroes those rows afterwards. RL_ESTATE while a
+ * batch is in flight or a restore is open (the rl_peek rule); RL_EINVAL when the range passes the
+ * loaded rule count.
+ *
+ * The rows are allocated at first use beside the rule table, one per rule id the table has room
+ * for, and keep their contents when rl_load_rules grows it; rules appended while batches are in
+ * flight need nothing new and start at 0. The counters are the service's, not the backend's
+ * state: rl_reset, restore and rl_resize leave them alone, only RL_RULE_STATS_CLEAR zeroes them.
+ * Rows are per rule id, so a caller that replaces rules (an id changes its meaning) reads and
+ * clears first. Out of scope: HipRateLimitCache (its ids name (limit, unit, shadow), not a stats
+ * key, and it walks every status on the host anyway), counting inside rl_router_step, and
+ * freecache's gauges. */
+typedef struct rl_rule_stat {     /* 64 B, one per rule id */
+  uint64_t total_hits;                  /* += max(1, hits_addend) per descriptor of the rule */
+  uint64_t over_limit;                  /* += over_limit_delta */
+  uint64_t near_limit;                  /* += near_limit_delta */
+  uint64_t over_limit_with_local_cache; /* += over_limit_delta when RL_FLAG_LOCAL_CACHE_HIT */
+  uint64_t shadow_mode;                 /* += 1 when RL_FLAG_SHADOW (the current, parity-unpinned definition) */
+  uint64_t reserved[3];                 /* 0 */
+} rl_rule_stat;
+enum { RL_RULE_STATS_CLEAR = 1u };
+int rl_rule_stats_add_device(rl_engine* e, const rl_batch* device_batch, const rl_status* d_out);
+int rl_rule_stats_read(rl_engine* e, uint32_t first_rule, uint32_t n, rl_rule_stat* out, uint32_t flags);
 
 /* ---- Descriptor-tree resolution (GetLimit) ------------------------
  * Replaces rateLimitConfigImpl.GetLimit (src/config/config_impl.go:274-323) per descriptor,
