@@ -60,6 +60,10 @@ struct PendingCall {
   // A control call (Save / Load) instead of a request: it keeps its place in the queue, and the
   // submitter runs it with nothing in flight. Returns an error message, empty on success.
   std::function<std::string()> ctl;
+  // HipRoutedRateLimitCache: a Peek (1) or Forget (2) instead of a request, answered at a rule /
+  // stop agreement into `peek`
+  int kind = 0;
+  std::vector<PeekStatus> peek;
 };
 
 namespace {
@@ -782,9 +786,10 @@ struct HipRoutedRateLimitCache::Step {
 
 namespace {
 // One rank's words in a rule / stop agreement (rl_router_allgather_host, RL_ROUTER_AG_MAX bytes).
-constexpr uint32_t SYNC_RULES = (RL_ROUTER_AG_MAX - 8) / sizeof(rl_rule);
+constexpr uint32_t SYNC_RULES = (RL_ROUTER_AG_MAX - 16) / sizeof(rl_rule);
 struct SyncWords {
   uint32_t stop, n;
+  uint32_t n_peek, n_forget;  // pending Peek / Forget calls of this rank
   rl_rule rules[SYNC_RULES];
 };
 static_assert(sizeof(SyncWords) <= RL_ROUTER_AG_MAX, "sync words");
@@ -895,20 +900,25 @@ bool HipRoutedRateLimitCache::known(const PendingCall& c) {
 // The rule / stop agreement (nothing in flight on any rank): every rank's new limits appended to
 // every rank's table in rank order (the first occurrence keeps its id), loaded into the engine.
 // Returns true when every rank asked to stop.
-bool HipRoutedRateLimitCache::sync(bool want_stop) {
+// Then the control calls: if any rank has pending Peeks every rank makes one rl_router_peek, then
+// the same for Forgets.
+bool HipRoutedRateLimitCache::sync(bool want_stop, std::deque<std::shared_ptr<PendingCall>>& ctl, uint64_t seq) {
   SyncWords mine;
   memset(&mine, 0, sizeof mine);
   mine.stop = want_stop ? 1u : 0u;
+  for (const auto& c : ctl) (c->kind == 1 ? mine.n_peek : mine.n_forget) += 1;
   mine.n = (uint32_t)std::min<size_t>(pending_.size(), SYNC_RULES);
   std::copy(pending_.begin(), pending_.begin() + mine.n, mine.rules);
   std::vector<SyncWords> all(r_.n_shards);
   int rc = rl_router_allgather_host(rt_, &mine, sizeof mine, all.data());
   if (rc) throw RedisError(std::string("rule agreement: ") + rl_router_last_error(rt_));
   n_syncs_ += 1;
-  bool all_stop = true;
+  bool all_stop = true, any_peek = false, any_forget = false;
   const size_t before = rules_.size();
   for (const SyncWords& w : all) {
     all_stop &= w.stop != 0;
+    any_peek |= w.n_peek != 0;
+    any_forget |= w.n_forget != 0;
     for (uint32_t i = 0; i < w.n; ++i) {
       const auto k = std::make_pair(w.rules[i].requests_per_unit, w.rules[i].unit);
       if (ids_.emplace(k, (uint32_t)rules_.size()).second) rules_.push_back(w.rules[i]);
@@ -922,7 +932,126 @@ bool HipRoutedRateLimitCache::sync(bool want_stop) {
     if (rc) throw RedisError(std::string("rl_load_rules: ") + rl_last_error(eng_));
     n_rules_ = rules_.size();
   }
+  if (any_peek) run_control(1, ctl, seq);
+  if (any_forget) run_control(2, ctl, seq);
   return all_stop;
+}
+
+// One collective rl_router_peek (kind 1) / rl_router_forget (kind 2) at an agreement: this rank's
+// pending calls of the kind whose limits are agreed, in enqueue order, as one request each, as far
+// as one router batch holds them (the others wait for the following agreement); an empty batch
+// when there are none.
+void HipRoutedRateLimitCache::run_control(int kind, std::deque<std::shared_ptr<PendingCall>>& ctl, uint64_t seq) {
+  std::vector<std::shared_ptr<PendingCall>> calls;
+  std::vector<uint8_t> blob;
+  std::vector<uint32_t> off(1, 0u), rule, req_of;
+  std::vector<int64_t> now;
+  const size_t max_blob = (size_t)s_.batch_limit * 128u;
+  for (auto it = ctl.begin(); it != ctl.end();) {
+    PendingCall& c = **it;
+    if (c.kind != kind || !known(c)) {
+      ++it;
+      continue;
+    }
+    if (rule.size() + c.prefix.size() > s_.batch_limit || now.size() + 1 > s_.batch_limit ||
+        blob.size() + c.blob_bytes > max_blob)
+      break;  // (enqueue order: the rest of the kind waits too)
+    if (trace_) trace_(c.req, seq, kTraceControl);
+    const uint32_t rq = (uint32_t)now.size();
+    now.push_back(ts_->UnixNow());
+    for (size_t i = 0; i < c.prefix.size(); ++i) {
+      const auto& lim = (*c.limits)[i];
+      blob.insert(blob.end(), c.prefix[i].begin(), c.prefix[i].end());
+      off.push_back((uint32_t)blob.size());
+      rule.push_back(lim ? ids_.at(limit_key(*lim)) : RL_NIL_RULE);
+      req_of.push_back(rq);
+    }
+    calls.push_back(*it);
+    it = ctl.erase(it);
+  }
+  rl_batch b;
+  memset(&b, 0, sizeof b);
+  b.n_desc = (uint32_t)rule.size();
+  b.n_req = (uint32_t)now.size();
+  b.blob_bytes = (uint32_t)blob.size();
+  b.prefix_blob = blob.data();
+  b.prefix_off = off.data();
+  b.rule_id = rule.data();
+  b.req_of = req_of.data();
+  b.now = now.data();
+  std::vector<rl_peek_reply> rep(std::max<size_t>(1, rule.size()));
+  rl_peek_reply* outs[1] = {rep.data()};
+  const int rc = kind == 1 ? rl_router_peek(rt_, &b, outs) : rl_router_forget(rt_, &b, outs);
+  if (rc) {
+    const std::string msg = rl_router_last_error(rt_);
+    fail(calls, msg);
+    if (rc == RL_ECOMM) throw RedisError(msg);  // the communicator is gone: the cache is broken
+    return;
+  }
+  size_t d = 0;
+  for (auto& cp : calls) {
+    PendingCall& c = *cp;
+    c.peek.resize(c.prefix.size());
+    for (size_t i = 0; i < c.prefix.size(); ++i, ++d) {
+      PeekStatus& s = c.peek[i];
+      s.Found = (rep[d].flags & RL_PEEK_FOUND) != 0;
+      s.LocalCached = (rep[d].flags & RL_PEEK_LOCAL_CACHED) != 0;
+      s.Count = rep[d].count;
+      s.TtlSeconds = rep[d].ttl_s;
+      s.CachedSeconds = rep[d].cached_s;
+    }
+    c.done.set_value();
+  }
+  done_calls(calls.size());
+}
+
+// Peek / Forget: the caller's side. GenerateCacheKey prefixes as DoLimit builds them (no hit, no
+// stat), queued behind the calls enqueued before; the submitter keeps it for the next agreement.
+std::vector<PeekStatus> HipRoutedRateLimitCache::peek_call(const RateLimitRequest& request,
+                                                           const std::vector<std::shared_ptr<RateLimit>>& limits,
+                                                           int kind) {
+  if (request.Descriptors.size() != limits.size())
+    throw std::logic_error("assert: len(request.Descriptors) == len(limits)");
+  auto call = std::make_shared<PendingCall>();
+  call->req = &request;
+  call->limits = &limits;
+  call->kind = kind;
+  call->prefix.resize(limits.size());
+  for (size_t i = 0; i < limits.size(); ++i) {
+    if (!limits[i]) continue;
+    std::string& p = call->prefix[i];
+    p = request.Domain;
+    p += '_';
+    for (const auto& e : request.Descriptors[i].Entries) {
+      p += e.Key;
+      p += '_';
+      p += e.Value;
+      p += '_';
+    }
+    call->blob_bytes += p.size();
+  }
+  if (limits.size() > s_.batch_limit || call->blob_bytes > (size_t)s_.batch_limit * 128u)
+    throw RedisError("hip backend: the request exceeds one router batch (HIP_BATCH_LIMIT)");
+  std::future<void> f = call->done.get_future();
+  {
+    std::lock_guard<std::mutex> g(mu_);
+    if (broken_) throw RedisError("hip backend: " + broken_msg_);
+    q_.push_back(call);
+    ++inflight_;
+  }
+  cv_.notify_one();
+  f.get();  // rethrows RedisError
+  return std::move(call->peek);
+}
+
+std::vector<PeekStatus> HipRoutedRateLimitCache::Peek(const RateLimitRequest& request,
+                                                      const std::vector<std::shared_ptr<RateLimit>>& limits) {
+  return peek_call(request, limits, 1);
+}
+
+std::vector<PeekStatus> HipRoutedRateLimitCache::Forget(const RateLimitRequest& request,
+                                                        const std::vector<std::shared_ptr<RateLimit>>& limits) {
+  return peek_call(request, limits, 2);
 }
 
 // The rank's step loop: rule / stop agreement every rule_sync_every steps (nothing in flight),
@@ -930,6 +1059,7 @@ bool HipRoutedRateLimitCache::sync(bool want_stop) {
 void HipRoutedRateLimitCache::submitter() {
   std::deque<Step> fl;
   std::deque<std::shared_ptr<PendingCall>> held;  // calls waiting for a rule agreement
+  std::deque<std::shared_ptr<PendingCall>> ctl;   // Peek / Forget calls waiting for the next agreement
   std::vector<rl_status> out;
   std::vector<uint32_t> thr;
   uint64_t seq = 0;
@@ -965,6 +1095,8 @@ void HipRoutedRateLimitCache::submitter() {
     }
     std::vector<std::shared_ptr<PendingCall>> rest(held.begin(), held.end());
     held.clear();
+    rest.insert(rest.end(), ctl.begin(), ctl.end());
+    ctl.clear();
     {
       std::lock_guard<std::mutex> g(mu_);
       broken_ = true;
@@ -982,9 +1114,9 @@ void HipRoutedRateLimitCache::submitter() {
         bool want_stop;
         {
           std::lock_guard<std::mutex> g(mu_);
-          want_stop = stop_ && q_.empty() && held.empty();
+          want_stop = stop_ && q_.empty() && held.empty() && ctl.empty();
         }
-        if (sync(want_stop)) break;  // every rank stops here
+        if (sync(want_stop, ctl, seq)) break;  // every rank stops here
         if (!held.empty()) {  // calls whose limits are agreed now go back to the front, in order
           std::lock_guard<std::mutex> g(mu_);
           for (auto it = held.rbegin(); it != held.rend(); ++it) q_.push_front(*it);
@@ -1001,6 +1133,12 @@ void HipRoutedRateLimitCache::submitter() {
           while (!q_.empty()) {
             std::shared_ptr<PendingCall> cp = q_.front();
             PendingCall& c = *cp;
+            if (c.kind) {  // a Peek / Forget: runs at the next agreement (its new limits are queued for it)
+              (void)known(c);
+              ctl.push_back(cp);
+              q_.pop_front();
+              continue;
+            }
             if (!known(c)) {  // waits for the next agreement
               held.push_back(cp);
               q_.pop_front();

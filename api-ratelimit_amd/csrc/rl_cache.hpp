@@ -143,11 +143,23 @@ class RateLimitCache {
 // One DoLimit call waiting in a micro-batcher (rl_cache.cpp).
 struct PendingCall;
 
+// What Peek / Forget of either cache report per descriptor (rl_hip.h rl_peek_reply).
+struct PeekStatus {
+  bool Found = false, LocalCached = false;
+  uint32_t Count = 0, TtlSeconds = 0, CachedSeconds = 0;
+};
+// The trace hook's position of a control call (Peek / Forget).
+constexpr uint32_t kTraceControl = 0xFFFFFFFFu;
+
 // Test hook of both batchers: every call's place in the serial order as it is put in a batch —
 // (the batch's / step's sequence number, the call's request position in it). The serial order
 // of one engine is (batch, position); of a routed deployment (step, rank, position). A Peek /
 // Forget of HipRateLimitCache is reported as (the next batch to be gathered, kTraceControl): it
-// comes after every call of the batches before that one and before every call of it.
+// comes after every call of the batches before that one and before every call of it. A Peek /
+// Forget of HipRoutedRateLimitCache runs at a rule / stop agreement and is reported as (the next
+// step, kTraceControl): after every call of the steps before that agreement on every rank, before
+// every call of the steps after it; within one agreement every rank's Peeks (rank order, enqueue
+// order) come before every rank's Forgets.
 using TraceFn = std::function<void(const RateLimitRequest* request, uint64_t seq, uint32_t pos)>;
 
 // HIP_* settings (BACKEND_TYPE=hip)
@@ -221,13 +233,10 @@ class HipRateLimitCache : public RateLimitCache {
   // (RequestsPerUnit, unit) is registered as DoLimit registers it. Errors throw RedisError.
   // HIP_LOCAL_CACHE=freecache: that cache lives on the host and is neither reported (LocalCached
   // is false) nor cleared; its entries expire after at most one divider.
-  // Out of scope: HipRoutedRateLimitCache (each rank's engine answers only for the keys it owns,
-  // the others read as absent: a routed peek is a later change) and a compact wire form.
-  struct PeekStatus {
-    bool Found = false, LocalCached = false;
-    uint32_t Count = 0, TtlSeconds = 0, CachedSeconds = 0;
-  };
-  static constexpr uint32_t kTraceControl = 0xFFFFFFFFu;
+  // HipRoutedRateLimitCache has its own Peek / Forget (below), which ask each key's owner. Out of
+  // scope: a compact wire form.
+  using PeekStatus = ratelimit::PeekStatus;
+  static constexpr uint32_t kTraceControl = ratelimit::kTraceControl;
   std::vector<PeekStatus> Peek(const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits);
   std::vector<PeekStatus> Forget(const RateLimitRequest& request,
                                  const std::vector<std::shared_ptr<RateLimit>>& limits);
@@ -353,6 +362,26 @@ class HipRoutedRateLimitCache : public RateLimitCache {
                           const std::vector<std::shared_ptr<RateLimit>>& limits) override;
   void Flush() override;
 
+  // Peek / Forget (rl_hip.h "Routed peek / forget"): HipRateLimitCache's calls, same signatures
+  // and PeekStatus, answered by the owner of each key through rl_router_peek / rl_router_forget.
+  // They are control calls agreed at the rule / stop agreement: every rank's agreement words carry
+  // its numbers of pending Peeks and Forgets; with nothing in flight on any rank, if any rank has
+  // pending Peeks every rank calls rl_router_peek once — its own pending calls as one request
+  // each, in enqueue order, at the time ts_->UnixNow() gives the submitter thread there; a rank
+  // with none passes an empty batch — and then, if any rank has pending Forgets, every rank calls
+  // rl_router_forget once the same way. Place in the serial order: after every call of the steps
+  // before that agreement and before every call of the steps after it; within one agreement all
+  // Peeks come before all Forgets (the trace hook reports (the next step's sequence number,
+  // kTraceControl)). A call whose limit has no agreed id yet queues the limit as DoLimit does and
+  // waits for the following agreement, as do calls beyond one router batch (batch_limit
+  // descriptors). Worst-case latency is therefore rule_sync_every x step_us (twice that for a new
+  // limit). Errors throw RedisError; a communicator failure marks the cache broken, as a step's.
+  using PeekStatus = ratelimit::PeekStatus;
+  static constexpr uint32_t kTraceControl = ratelimit::kTraceControl;
+  std::vector<PeekStatus> Peek(const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits);
+  std::vector<PeekStatus> Forget(const RateLimitRequest& request,
+                                 const std::vector<std::shared_ptr<RateLimit>>& limits);
+
   struct RoutedStats {
     uint64_t steps, empty_steps, rule_syncs, rules, held_calls;
   };
@@ -366,7 +395,10 @@ class HipRoutedRateLimitCache : public RateLimitCache {
   struct Step;
   void submitter();
   bool known(const PendingCall& c);
-  bool sync(bool want_stop);
+  bool sync(bool want_stop, std::deque<std::shared_ptr<PendingCall>>& ctl, uint64_t seq);
+  void run_control(int kind, std::deque<std::shared_ptr<PendingCall>>& ctl, uint64_t seq);
+  std::vector<PeekStatus> peek_call(const RateLimitRequest& request,
+                                    const std::vector<std::shared_ptr<RateLimit>>& limits, int kind);
   void fail(std::vector<std::shared_ptr<PendingCall>>& calls, const std::string& msg);
   void done_calls(size_t n);
 

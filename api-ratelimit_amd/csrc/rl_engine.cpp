@@ -77,6 +77,9 @@ void launch_v4_group(hipStream_t st, const rl_batch& b, const DevRule* rules, ui
                      const uint16_t* tstart);
 void launch_peek(hipStream_t, const rl_batch&, const DevRule*, uint32_t, uint64_t, const TableDesc&, rl_peek_reply*,
                  bool forget);
+void launch_peek_routed(hipStream_t, const RRec*, uint32_t, const DevRule*, uint32_t, const TableDesc&, rl_peek_reply*,
+                        bool forget);
+void launch_peek_unpack(hipStream_t, uint32_t, const uint32_t*, const rl_peek_reply*, rl_peek_reply*);
 void launch_rule_stats(hipStream_t, const rl_batch&, const rl_status*, uint32_t, rl_rule_stat*, const EngineCtl*, int,
                        uint32_t);
 }  // namespace rlhip
@@ -995,6 +998,7 @@ int rlx_engine_view(rl_engine* e, EngineView* v) {
   v->local_cache = e->cfg.local_cache ? 1 : 0;
   v->device = e->cfg.device;
   v->max_batch_desc = e->cfg.max_batch_desc;
+  v->stream = e->stream;
   return 0;
 }
 void rlx_engine_hot(rl_engine* e, std::vector<HotKey>& out) { out = e->hot; }
@@ -2235,6 +2239,39 @@ int rl_peek_device(rl_engine* e, const rl_batch* b, rl_peek_reply* d_out) {
   launch_peek(e->stream, *b, e->d_rules, e->n_rules, e->cfg.hash_seed, e->tab, d_out, false);
   const hipError_t he = hipGetLastError();
   if (he != hipSuccess) return e->hip_fail(he, "rl_peek_device");
+  return 0;
+}
+
+// Routed peek / forget, the engine's two pieces (rl_hip.h "Routed peek / forget").
+int rl_peek_routed(rl_engine* e, const void* d_records, uint32_t n, rl_peek_reply* d_reply, uint32_t flags) {
+  if (!e) return RL_EINVAL;
+  if (flags & ~(uint32_t)RL_PEEK_ROUTED_FORGET) return e->fail(RL_EINVAL, "unknown rl_peek_routed flags 0x%x", flags);
+  const bool forget = (flags & RL_PEEK_ROUTED_FORGET) != 0;
+  if (e->n_fl) return e->fail(RL_ESTATE, "rl_peek_routed while a batch is in flight (call rl_wait)");
+  if (e->restoring) return e->fail(RL_ESTATE, "rl_peek_routed between rl_restore_begin and rl_restore_end");
+  if (n && (!d_records || (!forget && !d_reply))) return e->fail(RL_EINVAL, "rl_peek_routed: null record or reply array");
+  if (!e->d_rules) {
+    const int rc = rl_load_rules(e, nullptr, 0);
+    if (rc) return rc;
+  }
+  if (!n) return 0;
+  const RRec* recs = reinterpret_cast<const RRec*>(d_records);
+  // the replies first (the state before the call, for every duplicate), then the clears
+  if (d_reply) launch_peek_routed(e->stream, recs, n, e->d_rules, e->n_rules, e->tab, d_reply, false);
+  if (forget) launch_peek_routed(e->stream, recs, n, e->d_rules, e->n_rules, e->tab, d_reply, true);
+  const hipError_t he = hipGetLastError();
+  if (he != hipSuccess) return e->hip_fail(he, "rl_peek_routed");
+  return 0;
+}
+
+int rl_route_unpack_peek(rl_engine* e, const rl_batch* b, const uint32_t* d_perm, const rl_peek_reply* d_back,
+                         rl_peek_reply* d_out) {
+  if (!e || !b) return RL_EINVAL;
+  if (!b->n_desc) return 0;
+  if (!d_perm || !d_back || !d_out) return e->fail(RL_EINVAL, "rl_route_unpack_peek: null routing buffer");
+  launch_peek_unpack(e->stream, b->n_desc, d_perm, d_back, d_out);
+  const hipError_t he = hipGetLastError();
+  if (he != hipSuccess) return e->hip_fail(he, "rl_route_unpack_peek");
   return 0;
 }
 

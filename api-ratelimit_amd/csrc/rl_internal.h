@@ -48,6 +48,7 @@ struct EngineView {
   int local_cache;
   int device;
   uint32_t max_batch_desc;
+  hipStream_t stream;  // the engine stream (rl_peek_routed / rl_route_unpack_peek run on it)
 };
 int rlx_engine_view(rl_engine* e, EngineView* v);
 // A router's engine keeps SECOND key strings findable up to 3 s behind its newest time

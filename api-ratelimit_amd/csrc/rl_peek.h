@@ -1,0 +1,70 @@
+// rl_peek.h — the lookup both peek kernels end in (rl_peek.hip k_peek: from a descriptor;
+// rl_peek_routed.hip k_peek_routed: from a routed record), one function so the two cannot drift.
+#pragma once
+#include "rl_decide.h"
+
+namespace rlhip {
+namespace peek {
+
+constexpr int NT = 256;
+
+// From a key's prefix state, its request time (in [0, MAX_NOW], checked by the caller) and its
+// rule: the window start, the key string's identity and table place, the lookup (issued first:
+// the key's first slot, then table_find's bounded probe), the store choice, and the reply
+// (!FORGET: rep with its words filled in) or the clears (FORGET: separate 32-bit stores, rep as
+// it came). The reply goes in and out by value: by reference k_peek compiled to a longer probe
+// loop and measured 1 % slower than before the function existed ("Peek").
+template <bool FORGET>
+__device__ __forceinline__ rl_peek_reply peek_key(const FpState& s, const uint32_t n32, const DevRule& rr,
+                                                  const TableDesc& tab, rl_peek_reply rep) {
+  // now / divider by 32-bit multiply-high (rl_tile.h key_of: exact for every 32-bit now)
+  const uint32_t q60 = __umulhi(n32, 0x88888889u) >> 5, q3600 = __umulhi(n32, 0x91A2B3C5u) >> 11,
+                 q86400 = __umulhi(n32 >> 7, 0xC22E4507u) >> 9;
+  const uint32_t unit = rr.unit;
+  const uint32_t widx = unit == RL_UNIT_SECOND ? n32 : unit == RL_UNIT_MINUTE ? q60 : unit == RL_UNIT_HOUR ? q3600 : q86400;
+  const uint32_t ws = widx * rr.div;  // (now/divider)*divider  cache_key.go:66-68
+  uint64_t hi, lo;
+  fp_final(s, (uint64_t)ws, hi, lo);
+  const Place pl = place_of(ws);
+  const uint64_t key = make_sort_key(pl.region, hi);
+  const SlotView pre = load_slot(slot_first(tab, key));
+  Slot* slot = nullptr;
+  KeyState st{0, 0, 0, 0};
+  const bool have = table_find(tab, key, lo, pl.gen, pre, slot, st);
+  const bool ps = per_second_store(tab, unit);
+  if (!FORGET) {
+    rep.flags = ps ? RL_PEEK_PER_SECOND : 0u;
+    if (have) {
+      if (ps) {
+        if (st.pcount) {
+          rep.flags |= RL_PEEK_FOUND;
+          rep.count = st.pcount;
+        }
+      } else if (n32 < st.exp) {
+        rep.flags |= RL_PEEK_FOUND;
+        rep.count = st.count;
+        rep.ttl_s = st.exp - n32;
+      }
+      if (tab.local_cache && n32 < st.frz) {
+        rep.flags |= RL_PEEK_LOCAL_CACHED;
+        rep.cached_s = st.frz - n32;
+      }
+    }
+  } else if (have) {
+    // DEL on the descriptor's store, and the string leaves the local cache. One 32-bit store
+    // per word: another lane of this launch may be clearing the other store of this slot. The
+    // claim word and the key stay: the slot remains the string's for its generation (open
+    // addressing without tombstones), and the next INCRBY starts from 0.
+    if (ps) {
+      slot->pcount = 0u;
+    } else {
+      slot->count = 0u;
+      slot->exp = 0u;
+    }
+    slot->frz = 0u;
+  }
+  return rep;
+}
+
+}  // namespace peek
+}  // namespace rlhip

@@ -7,12 +7,10 @@
 // before the call, and two descriptors that clear the two stores of one string lose nothing.
 #include <hip/hip_runtime.h>
 
-#include "rl_decide.h"
+#include "rl_peek.h"
 
 namespace rlhip {
 namespace peek {
-
-constexpr int NT = 256;
 
 // The loads of a lane go out in three dependent levels, each issued as one run and waited for
 // once (the kernel is latency-bound: random 32-B reads): (offsets, rule id, request index),
@@ -21,7 +19,7 @@ constexpr int NT = 256;
 // clamped reads stay inside the arrays (n_desc >= 1 in a launched kernel, n_req >= 1 and a rule
 // table allocation exist, both host-checked) and inside the blob's RL_BLOB_SLACK readable bytes.
 // No LDS, no lane waits for another; the loops are bounded by the prefix length (hash) and the
-// region size (probe).
+// region size (probe). The third level and everything behind it is rl_peek.h's peek_key.
 template <bool FORGET>
 __global__ __launch_bounds__(NT) void k_peek(const DevBatch in, const DevRule* __restrict__ rules, const uint32_t n_rules,
                                              const uint64_t seed, const TableDesc tab, rl_peek_reply* __restrict__ out) {
@@ -54,53 +52,7 @@ __global__ __launch_bounds__(NT) void k_peek(const DevBatch in, const DevRule* _
   rep.flags = nil ? RL_PEEK_NIL : RL_PEEK_BAD;
   if (ok) {
     const FpState s = prefix_state_pre(w0, w1, in.blob, o0, len, seed);
-    // now / divider by 32-bit multiply-high (rl_tile.h key_of: exact for every 32-bit now)
-    const uint32_t n32 = (uint32_t)now;
-    const uint32_t q60 = __umulhi(n32, 0x88888889u) >> 5, q3600 = __umulhi(n32, 0x91A2B3C5u) >> 11,
-                   q86400 = __umulhi(n32 >> 7, 0xC22E4507u) >> 9;
-    const uint32_t unit = rr.unit;
-    const uint32_t widx = unit == RL_UNIT_SECOND ? n32 : unit == RL_UNIT_MINUTE ? q60 : unit == RL_UNIT_HOUR ? q3600 : q86400;
-    const uint32_t ws = widx * rr.div;  // (now/divider)*divider  cache_key.go:66-68
-    uint64_t hi, lo;
-    fp_final(s, (uint64_t)ws, hi, lo);
-    const Place pl = place_of(ws);
-    const uint64_t key = make_sort_key(pl.region, hi);
-    const SlotView pre = load_slot(slot_first(tab, key));
-    Slot* slot = nullptr;
-    KeyState st{0, 0, 0, 0};
-    const bool have = table_find(tab, key, lo, pl.gen, pre, slot, st);
-    const bool ps = per_second_store(tab, unit);
-    if (!FORGET) {
-      rep.flags = ps ? RL_PEEK_PER_SECOND : 0u;
-      if (have) {
-        if (ps) {
-          if (st.pcount) {
-            rep.flags |= RL_PEEK_FOUND;
-            rep.count = st.pcount;
-          }
-        } else if (n32 < st.exp) {
-          rep.flags |= RL_PEEK_FOUND;
-          rep.count = st.count;
-          rep.ttl_s = st.exp - n32;
-        }
-        if (tab.local_cache && n32 < st.frz) {
-          rep.flags |= RL_PEEK_LOCAL_CACHED;
-          rep.cached_s = st.frz - n32;
-        }
-      }
-    } else if (have) {
-      // DEL on the descriptor's store, and the string leaves the local cache. One 32-bit store
-      // per word: another lane of this launch may be clearing the other store of this slot. The
-      // claim word and the key stay: the slot remains the string's for its generation (open
-      // addressing without tombstones), and the next INCRBY starts from 0.
-      if (ps) {
-        slot->pcount = 0u;
-      } else {
-        slot->count = 0u;
-        slot->exp = 0u;
-      }
-      slot->frz = 0u;
-    }
+    rep = peek_key<FORGET>(s, (uint32_t)now, rr, tab, rep);
   }
   if (!FORGET) out[i] = rep;
 }

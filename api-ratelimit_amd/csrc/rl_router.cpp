@@ -410,6 +410,12 @@ struct Shard {
   uint32_t last_tot[HOT_MAX] = {};  // sums of hits per group, last step that combined
   bool last_valid = false;
   bool repacked = false;            // since the last refresh
+  // routed peek / forget (allocated at the first call): the owner's replies, the origin's replies
+  // strided like send, and without RL_ROUTER_HOST the input staging (pinned + device)
+  rl_peek_reply* pk_reply = nullptr;
+  rl_peek_reply* pk_back = nullptr;
+  uint8_t* pk_h_in = nullptr;
+  uint8_t* pk_d_in = nullptr;
 };
 
 struct StepSlot {
@@ -523,7 +529,13 @@ struct rl_router {
   void free_all();
   int validate(const rl_batch& b) const;
   int stage_host(uint32_t s, uint32_t k, const rl_batch& hb, rl_batch& db);
-  void pack(uint32_t s, uint32_t k);
+  void pack(uint32_t s, uint32_t k, bool plain = false);
+  int peek_validate(const rl_batch& b, uint32_t n_rules, std::string& why) const;
+  int peek_alloc(Shard& S);
+  int peek_stage(uint32_t s, uint32_t k, const rl_batch& hb, rl_batch& db);
+  int peek(const rl_batch* batches, rl_peek_reply* const* out, bool forget);
+  int peek_coll(uint32_t k, rl_peek_reply* const* out, bool forget);
+  int peek_local(uint32_t k, rl_peek_reply* const* out, bool forget);
   void note_combine(uint32_t s, uint32_t k);
   void refresh_hot();
   int check_config();
@@ -551,6 +563,9 @@ void rl_router::free_all() {
       for (void* p : {(void*)t.h_x, (void*)t.hs.h_in, (void*)t.hs.h_out, (void*)t.hs.h_thr})
         if (p) (void)hipHostFree(p);
     }
+    for (void* p : {(void*)s.pk_reply, (void*)s.pk_back, (void*)s.pk_d_in})
+      if (p) (void)hipFree(p);
+    if (s.pk_h_in) (void)hipHostFree(s.pk_h_in);
     if (s.d_hot) (void)hipFree(s.d_hot);
     if (s.h_hot) (void)hipHostFree(s.h_hot);
     if (s.ev_hot) (void)hipEventDestroy(s.ev_hot);
@@ -673,7 +688,8 @@ int rl_router::stage_host(uint32_t s, uint32_t k, const rl_batch& b, rl_batch& d
 // Origin pack of shard s for slot k on its origin stream: the (count, status, tmin, tmax) words
 // land in d_x[0, XS G) and, with combining, the groups' sums and the control words in the
 // pinned mirror.
-void rl_router::pack(uint32_t s, uint32_t k) {
+// plain: one record per descriptor whatever the route hot set holds (routed peek / forget).
+void rl_router::pack(uint32_t s, uint32_t k, bool plain) {
   Shard& S = sh[s];
   ShardStep& t = S.st[k];
   const uint32_t G = cfg.n_shards;
@@ -696,7 +712,7 @@ void rl_router::pack(uint32_t s, uint32_t k) {
   }
   // (no combining with EXPIRE jitter: a combined record's EXPIRE would need the group's last
   // descriptor's jitter)
-  const bool combine = !(cfg.flags & RL_ROUTER_NO_COMBINE) && !S.v.local_cache && !S.hot.empty() && !t.b.ttl_jitter;
+  const bool combine = !plain && !(cfg.flags & RL_ROUTER_NO_COMBINE) && !S.v.local_cache && !S.hot.empty() && !t.b.ttl_jitter;
   if (!t.zeroed) (void)hipMemsetAsync(t.zero, 0, t.zero_bytes, S.os);  // (the slot's last step had no unpack)
   t.pb.thr = t.thr;  // zeroed by the pack
   // the hot scan writes the group sums and its verdict straight into the pinned mirror
@@ -1493,7 +1509,325 @@ int rl_router::wait(rl_status* const* out, uint32_t* const* thr, bool into) {
   return rc;
 }
 
+// ---- routed peek / forget (rl_hip.h "Routed peek / forget") --------------------------------
+// With nothing in flight every step slot is free: the call runs in the slot after the next
+// submit's (rl_router_host_acquire may have handed that one's staging out already) and uses its
+// send / perm / recv / d_x buffers and the step's pack; only the reply buffers are its own.
+
+// What the call refuses before anything is staged: rl_peek's list, and the router's capacities.
+int rl_router::peek_validate(const rl_batch& b, uint32_t n_rules, std::string& why) const {
+  char buf[160];
+  auto bad = [&](int code, const char* fmt, unsigned i, long long v) {
+    snprintf(buf, sizeof buf, fmt, i, v);
+    why = buf;
+    return code;
+  };
+  if (b.n_desc > cfg.max_desc || b.n_req > cfg.max_desc || (size_t)b.blob_bytes + RL_BLOB_SLACK > o_off)
+    return bad(RL_ECAPACITY, "batch exceeds the router's capacity (max_desc %u, %lld blob bytes)", cfg.max_desc,
+               (long long)(o_off - RL_BLOB_SLACK));
+  if (b.reserved || (b.n_desc && !b.n_req)) return bad(RL_EINVAL, "reserved word or descriptors without requests", 0, 0);
+  if (b.n_desc && (!b.prefix_off || !b.rule_id || !b.req_of || (b.blob_bytes && !b.prefix_blob)))
+    return bad(RL_EINVAL, "null descriptor array", 0, 0);
+  if (b.n_req && !b.now) return bad(RL_EINVAL, "null request times", 0, 0);
+  for (uint32_t r = 0; r < b.n_req; ++r)
+    if (b.now[r] < 0 || b.now[r] > MAX_NOW) return bad(RL_EINVAL, "request %u: time %lld outside [0, 0xFFFD0000]", r, b.now[r]);
+  for (uint32_t i = 0; i < b.n_desc; ++i) {
+    if (b.prefix_off[i] > b.prefix_off[i + 1] || b.prefix_off[i + 1] > b.blob_bytes)
+      return bad(RL_EINVAL, "descriptor %u: prefix offsets out of order or past blob_bytes", i, 0);
+    if (b.req_of[i] >= b.n_req || (i && b.req_of[i] < b.req_of[i - 1]))
+      return bad(RL_EINVAL, "descriptor %u: request index %lld decreases or is not below n_req", i, b.req_of[i]);
+    if (b.rule_id[i] != RL_NIL_RULE && (b.rule_id[i] >= n_rules || b.rule_id[i] >= RREC_MAX_RULE))
+      return bad(RL_EINVAL, "descriptor %u: unknown rule id %lld (or not below 0xFFFF)", i, b.rule_id[i]);
+  }
+  return 0;
+}
+
+int rl_router::peek_alloc(Shard& S) {
+  if (S.pk_reply && S.pk_back && ((cfg.flags & RL_ROUTER_HOST) || (S.pk_d_in && S.pk_h_in))) return 0;
+  const size_t n = (size_t)cfg.max_desc * cfg.n_shards * sizeof(rl_peek_reply);
+  hipError_t he = hipSuccess;
+  if (!S.pk_reply) he = hipMalloc(&S.pk_reply, n);
+  if (he == hipSuccess && !S.pk_back) he = hipMalloc(&S.pk_back, n);
+  if (!(cfg.flags & RL_ROUTER_HOST)) {
+    if (he == hipSuccess && !S.pk_d_in) he = hipMalloc(&S.pk_d_in, in_bytes);
+    if (he == hipSuccess && !S.pk_h_in) he = hipHostMalloc(&S.pk_h_in, in_bytes, hipHostMallocDefault);
+  }
+  return he == hipSuccess ? 0 : RL_EHIP;
+}
+
+// A validated host batch -> pinned staging -> device on the shard's origin stream, in the step's
+// staging layout; hits_addend staged as zeros, no jitter.
+int rl_router::peek_stage(uint32_t s, uint32_t k, const rl_batch& b, rl_batch& d) {
+  Shard& S = sh[s];
+  const bool host = (cfg.flags & RL_ROUTER_HOST) != 0;
+  uint8_t* h = host ? S.st[k].hs.h_in : S.pk_h_in;
+  uint8_t* dv = host ? S.st[k].hs.d_in : S.pk_d_in;
+  d = rl_batch{};
+  if (!b.n_desc) return 0;
+  struct Arr { const void* src; size_t o, n; } arrs[] = {
+      {b.prefix_blob, 0, b.blob_bytes}, {b.prefix_off, o_off, ((size_t)b.n_desc + 1) * 4},
+      {b.rule_id, o_rule, (size_t)b.n_desc * 4}, {b.req_of, o_req, (size_t)b.n_desc * 4},
+      {b.now, o_now, (size_t)b.n_req * 8}, {nullptr, o_hits, (size_t)b.n_req * 4}};
+  for (auto& a : arrs) {
+    if (a.n && a.src) memcpy(h + a.o, a.src, a.n);
+    else if (a.n) memset(h + a.o, 0, a.n);
+  }
+  memset(h + b.blob_bytes, 0, RL_BLOB_SLACK);  // the device reads prefixes in 16-B words
+  arrs[0].n += RL_BLOB_SLACK;
+  hipError_t he = hipSuccess;
+  for (auto& a : arrs)
+    if (he == hipSuccess) he = hipMemcpyAsync(dv + a.o, h + a.o, a.n, hipMemcpyHostToDevice, S.os);
+  if (he != hipSuccess) return RL_EHIP;
+  d.n_desc = b.n_desc;
+  d.n_req = b.n_req;
+  d.blob_bytes = b.blob_bytes;
+  d.prefix_blob = dv;
+  d.prefix_off = reinterpret_cast<const uint32_t*>(dv + o_off);
+  d.rule_id = reinterpret_cast<const uint32_t*>(dv + o_rule);
+  d.req_of = reinterpret_cast<const uint32_t*>(dv + o_req);
+  d.now = reinterpret_cast<const int64_t*>(dv + o_now);
+  d.hits_addend = reinterpret_cast<const uint32_t*>(dv + o_hits);
+  return 0;
+}
+
+int rl_router::peek(const rl_batch* batches, rl_peek_reply* const* out, bool forget) {
+  const char* what = forget ? "rl_router_forget" : "rl_router_peek";
+  if (broken) return fail(RL_ECOMM, "the router's communicator was aborted after a transport failure");
+  if (done != seq) return fail(RL_ESTATE, "%s with a routed step in flight: call rl_router_wait", what);
+  const uint32_t k = (uint32_t)((seq + 1) % NSLOT), nl = n_local();
+  for (uint32_t s = 0; s < nl; ++s) {
+    Shard& S = sh[s];
+    ShardStep& t = S.st[k];
+    t.rc_pack = t.rc_dec = t.rc_local = 0;
+    t.late = false;
+    t.msg.clear();
+    t.phase = "pack";
+    t.n_sub = t.n_runs = t.n_in = 0;
+    t.out = nullptr;
+    t.thr = nullptr;
+    int rc = rlx_engine_view(S.e, &S.v);  // (rules may have been appended since)
+    if (rc) t.msg = rl_last_error(S.e);
+    if (!rc) rc = peek_validate(batches[s], S.v.n_rules, t.msg);
+    if (!rc && !forget && batches[s].n_desc && (!out || !out[s])) {
+      rc = RL_EINVAL;
+      t.msg = "null reply array";
+    }
+    if (!rc && (rc = peek_alloc(S))) t.msg = "reply buffer / staging allocation failed";
+    if (!rc && (rc = peek_stage(s, k, batches[s], t.b))) t.msg = "host staging copy failed";
+    if (rc) t.b = rl_batch{};
+    t.rc_pack = rc;
+    pack(s, k, true);
+    if (!coll) (void)hipStreamSynchronize(S.os);
+  }
+  return coll ? peek_coll(k, out, forget) : peek_local(k, out, forget);
+}
+
+static const char* const kPackRefused =
+    "route pack: the device refused the batch (unknown rule id or request index, malformed prefix offsets, a time "
+    "outside [0, 0xFFFD0000], or its look-back spin limit expired)";
+
+// Collective transports: counts (+ every origin's status), records, the owner's lookup on the
+// engine stream, then its status and the replies back, the origin's unpack on the engine stream.
+// The streams hand over by events; the host waits once, bounded, at the end of each half.
+int rl_router::peek_coll(uint32_t k, rl_peek_reply* const* out, bool forget) {
+  const char* what = forget ? "rl_router_forget" : "rl_router_peek";
+  const uint32_t G = cfg.n_shards, me = cfg.rank;
+  const size_t D = cfg.max_desc;
+  Shard& S = sh[0];
+  ShardStep& t = S.st[k];
+  hipStream_t es = S.v.stream;
+  hipError_t he = hipSuccess;
+  if (rs != S.os) {
+    he = hipEventRecord(S.ev, S.os);
+    if (he == hipSuccess) he = hipStreamWaitEvent(rs, S.ev, 0);
+  }
+  ncclResult_t nr = xp->a2a(t.d_x, t.d_x + XS * G, 4 * XS, rs);
+  if (nr != ncclSuccess) return nccl_fail(nr, "all-to-all(peek counts)");
+  if (he == hipSuccess) he = hipMemcpyAsync(t.h_x, t.d_x, 8 * XS * G, hipMemcpyDeviceToHost, rs);
+  if (he == hipSuccess) he = hipEventRecord(ev_cnt, rs);
+  if (he == hipSuccess)
+    if (int rc = wait_bounded(ev_cnt, nullptr, "all-to-all(peek counts)", &he)) return rc;
+  if (he != hipSuccess) {  // the counts are unknown: nobody can take part in the record exchange
+    abort_comm();
+    return fail(RL_ECOMM, "%s: counts exchange: %s (communicator aborted)", what, hipGetErrorString(he));
+  }
+  const int32_t* hs = t.h_x;
+  const int32_t* hr = t.h_x + XS * G;
+  if (!t.rc_pack && hs[1]) {
+    t.rc_pack = hs[1];
+    t.msg = kPackRefused;
+  }
+  int bad = -1;
+  for (uint32_t j = 0; j < G && bad < 0; ++j)
+    if (hr[XS * j + 1]) bad = (int)j;
+  if (bad >= 0) {  // every rank saw the same status words: all leave here, nothing looked up or cleared
+    if (t.rc_pack) return fail(t.rc_pack, "%s: shard %u: %s", what, me, t.msg.c_str());
+    return fail(RL_EPEER, "%s: shard %d refused its batch with %d: nothing was looked up or cleared", what, bad,
+                (int)hr[XS * bad + 1]);
+  }
+  size_t sc[MAXS], sd[MAXS], rc[MAXS], rd[MAXS];
+  uint64_t ro = 0;
+  for (uint32_t j = 0; j < G; ++j) {
+    t.cnt[j] = (uint32_t)hs[XS * j];
+    t.rcv[j] = (uint32_t)hr[XS * j];
+    sc[j] = (size_t)t.cnt[j] * REC;
+    sd[j] = j * D * REC;
+    rc[j] = (size_t)t.rcv[j] * REC;
+    rd[j] = ro;
+    ro += rc[j];
+  }
+  t.n_in = (uint32_t)(ro / REC);
+  nr = xp->a2av(t.pb.send, sc, sd, t.recv, rc, rd, rs);
+  if (nr != ncclSuccess) return nccl_fail(nr, "all-to-all-v(peek records)");
+  // owner: everything received, origin-major, on the engine stream behind the records
+  int mine = 0;
+  he = hipEventRecord(ev_rs, rs);
+  if (he == hipSuccess) he = hipStreamWaitEvent(es, ev_rs, 0);
+  if (he == hipSuccess) {
+    mine = rl_peek_routed(S.e, t.recv, t.n_in, S.pk_reply, forget ? (uint32_t)RL_PEEK_ROUTED_FORGET : 0u);
+    if (mine) t.msg = rl_last_error(S.e);
+  }
+  if (he == hipSuccess) he = hipEventRecord(S.ev, es);
+  if (he == hipSuccess) he = hipStreamWaitEvent(rs, S.ev, 0);
+  if (he != hipSuccess && !mine) {
+    mine = RL_EHIP;
+    t.msg = std::string("owner lookup: ") + hipGetErrorString(he);
+  }
+  // this rank's status word to every origin (a step's reply exchange: zero words on success, else
+  // uploaded over the failure words the pack wrote), and the replies: to origin j the replies to
+  // its records (compact), into its back buffer at my section
+  int32_t* hw = t.h_x + 2 * XS * G;
+  for (uint32_t j = 0; j < G; ++j) hw[j] = mine;
+  const int32_t* sw = d_ok;
+  if (mine) {
+    sw = t.d_x + 2 * XS * G;
+    (void)hipMemcpyAsync(t.d_x + 2 * XS * G, hw, 4 * G, hipMemcpyHostToDevice, rs);
+  }
+  uint64_t so = 0;
+  for (uint32_t j = 0; j < G; ++j) {
+    sc[j] = (size_t)t.rcv[j] * sizeof(rl_peek_reply);
+    sd[j] = so;
+    so += sc[j];
+    rc[j] = (size_t)t.cnt[j] * sizeof(rl_peek_reply);
+    rd[j] = j * D * sizeof(rl_peek_reply);  // perm = owner * D + position
+  }
+  nr = xp->group_start();
+  if (nr == ncclSuccess) nr = xp->a2a(sw, t.d_x + 2 * XS * G + G, 4, rs);
+  if (nr == ncclSuccess) nr = xp->a2av(S.pk_reply, sc, sd, S.pk_back, rc, rd, rs);
+  const ncclResult_t ne = xp->group_end();
+  if (nr != ncclSuccess || ne != ncclSuccess) return nccl_fail(nr != ncclSuccess ? nr : ne, "all-to-all(peek replies)");
+  // origin: the owners' statuses to the host, the unpack on the engine stream behind the replies
+  // (into the slot's record buffer: the owner's lookup, its last reader, is ahead on that stream)
+  rl_peek_reply* d_out = reinterpret_cast<rl_peek_reply*>(t.recv);
+  int32_t* hst = t.h_x + 2 * XS * G + G;
+  he = hipMemcpyAsync(hst, t.d_x + 2 * XS * G + G, 4 * G, hipMemcpyDeviceToHost, rs);
+  if (he == hipSuccess) he = hipEventRecord(ev_rs, rs);
+  if (he == hipSuccess) he = hipStreamWaitEvent(es, ev_rs, 0);
+  int rc_un = 0;
+  if (he == hipSuccess) rc_un = rl_route_unpack_peek(S.e, &t.b, t.pb.perm, S.pk_back, d_out);
+  if (he == hipSuccess) he = hipEventRecord(S.ev, es);
+  if (he == hipSuccess) {
+    hipError_t hw2 = hipSuccess;
+    if (int rcw = wait_bounded(S.ev, nullptr, "all-to-all(peek replies)", &hw2)) return rcw;
+    he = hw2;
+  } else {
+    // after a failure to enqueue: drain the exchange stream (bounded), the statuses are lost
+    if (int rcw = wait_bounded(nullptr, rs, "all-to-all(peek replies)", nullptr)) return rcw;
+  }
+  if (mine) return fail(mine, "%s: shard %u (owner lookup): %s", what, me, t.msg.c_str());
+  if (he != hipSuccess) return fail(RL_EHIP, "%s: reply exchange / unpack: %s", what, hipGetErrorString(he));
+  for (uint32_t j = 0; j < G; ++j)
+    if (hst[j]) return fail(RL_EPEER, "%s: owner %u failed its lookup with %d", what, j, (int)hst[j]);
+  if (rc_un) return fail(rc_un, "%s: unpack: %s", what, rl_last_error(S.e));
+  if (out && out[0] && t.b.n_desc) {
+    he = hipMemcpy(out[0], d_out, (size_t)t.b.n_desc * sizeof(rl_peek_reply), hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return fail(RL_EHIP, "%s: reply copy: %s", what, hipGetErrorString(he));
+  }
+  return 0;
+}
+
+// Local transport: the same exchanges by device copies, the owners one after another.
+int rl_router::peek_local(uint32_t k, rl_peek_reply* const* out, bool forget) {
+  const char* what = forget ? "rl_router_forget" : "rl_router_peek";
+  const uint32_t G = cfg.n_shards;
+  const size_t D = cfg.max_desc;
+  for (uint32_t s = 0; s < G; ++s) {
+    ShardStep& t = sh[s].st[k];
+    hipError_t he = hipMemcpyAsync(t.h_x, t.d_x, 4 * XS * G, hipMemcpyDeviceToHost, sh[s].os);
+    if (he == hipSuccess) he = hipStreamSynchronize(sh[s].os);
+    if (he != hipSuccess && !t.rc_pack) {
+      t.rc_pack = RL_EHIP;
+      t.msg = std::string("counts: ") + hipGetErrorString(he);
+    }
+    if (!t.rc_pack && t.h_x[1]) {
+      t.rc_pack = t.h_x[1];
+      t.msg = kPackRefused;
+    }
+  }
+  for (uint32_t s = 0; s < G; ++s)  // nothing looked up or cleared anywhere
+    if (sh[s].st[k].rc_pack) return fail(sh[s].st[k].rc_pack, "%s: shard %u: %s", what, s, sh[s].st[k].msg.c_str());
+  hipError_t he = hipSuccess;
+  for (uint32_t j = 0; j < G; ++j) {  // owner j: origin 0's section j, then origin 1's, ...
+    ShardStep& tj = sh[j].st[k];
+    uint64_t o = 0;
+    for (uint32_t i = 0; i < G; ++i) {
+      const uint32_t c = (uint32_t)sh[i].st[k].h_x[XS * j];
+      sh[i].st[k].cnt[j] = c;
+      tj.rcv[i] = c;
+      if (c && he == hipSuccess)
+        he = hipMemcpyAsync(tj.recv + o, sh[i].st[k].pb.send + j * D, (size_t)c * REC, hipMemcpyDeviceToDevice, rs);
+      o += c;
+    }
+    tj.n_in = (uint32_t)o;
+  }
+  if (he == hipSuccess) he = hipStreamSynchronize(rs);
+  if (he != hipSuccess) return fail(RL_EHIP, "%s: record exchange: %s", what, hipGetErrorString(he));
+  for (uint32_t j = 0; j < G; ++j) {
+    ShardStep& t = sh[j].st[k];
+    const int rc = rl_peek_routed(sh[j].e, t.recv, t.n_in, sh[j].pk_reply, forget ? (uint32_t)RL_PEEK_ROUTED_FORGET : 0u);
+    if (rc) return fail(rc, "%s: shard %u (owner lookup): %s", what, j, rl_last_error(sh[j].e));
+    he = hipStreamSynchronize(sh[j].v.stream);
+    if (he != hipSuccess) return fail(RL_EHIP, "%s: shard %u (owner lookup): %s", what, j, hipGetErrorString(he));
+  }
+  for (uint32_t j = 0; j < G; ++j) {  // owner j's replies, origin-major, into each origin's section j
+    uint64_t o = 0;
+    for (uint32_t i = 0; i < G; ++i) {
+      const uint32_t c = sh[j].st[k].rcv[i];
+      if (c && he == hipSuccess)
+        he = hipMemcpyAsync(sh[i].pk_back + j * D, sh[j].pk_reply + o, (size_t)c * sizeof(rl_peek_reply),
+                            hipMemcpyDeviceToDevice, rs);
+      o += c;
+    }
+  }
+  if (he == hipSuccess) he = hipStreamSynchronize(rs);
+  if (he != hipSuccess) return fail(RL_EHIP, "%s: reply exchange: %s", what, hipGetErrorString(he));
+  for (uint32_t i = 0; i < G; ++i) {  // (into the slot's record buffer: its lookup is done)
+    ShardStep& t = sh[i].st[k];
+    const int rc = rl_route_unpack_peek(sh[i].e, &t.b, t.pb.perm, sh[i].pk_back, reinterpret_cast<rl_peek_reply*>(t.recv));
+    if (rc) return fail(rc, "%s: shard %u (unpack): %s", what, i, rl_last_error(sh[i].e));
+    he = hipStreamSynchronize(sh[i].v.stream);
+    if (he != hipSuccess) return fail(RL_EHIP, "%s: shard %u (unpack): %s", what, i, hipGetErrorString(he));
+  }
+  for (uint32_t i = 0; i < G; ++i) {
+    const ShardStep& t = sh[i].st[k];
+    if (!out || !out[i] || !t.b.n_desc) continue;
+    he = hipMemcpy(out[i], t.recv, (size_t)t.b.n_desc * sizeof(rl_peek_reply), hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return fail(RL_EHIP, "%s: reply copy: %s", what, hipGetErrorString(he));
+  }
+  return 0;
+}
+
 extern "C" {
+
+int rl_router_peek(rl_router* r, const rl_batch* host_batches, rl_peek_reply* const* out) {
+  if (!r || !host_batches || !out) return RL_EINVAL;
+  return r->peek(host_batches, out, false);
+}
+
+int rl_router_forget(rl_router* r, const rl_batch* host_batches, rl_peek_reply* const* out_or_null) {
+  if (!r || !host_batches) return RL_EINVAL;
+  return r->peek(host_batches, out_or_null, true);
+}
 
 int rl_router_unique_id(uint8_t* id_out) {
   if (!id_out) return RL_EINVAL;

@@ -117,6 +117,7 @@ RAW_DTYPE = np.dtype([("after", "<u4"), ("flags", "<u4")])
 # ---- peek / forget (rl_hip.h "Peek / forget") ----
 PEEK_FOUND, PEEK_LOCAL_CACHED, PEEK_NIL, PEEK_PER_SECOND, PEEK_BAD = 1, 2, 4, 8, 16  # rl_peek_reply.flags
 PEEK_DTYPE = np.dtype([("count", "<u4"), ("ttl_s", "<u4"), ("cached_s", "<u4"), ("flags", "<u4")])
+PEEK_ROUTED_FORGET = 1  # RL_PEEK_ROUTED_FORGET: rl_peek_routed clears after it has looked every record up
 
 
 # ---- rule stats (rl_hip.h "Rule stats") ----
@@ -274,6 +275,10 @@ ABI = [
     ("rl_peek", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
     ("rl_peek_device", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
     ("rl_forget", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
+    ("rl_peek_routed", [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32], C.c_int),
+    ("rl_route_unpack_peek", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    ("rl_router_peek", [C.c_void_p, C.POINTER(RlBatch), C.POINTER(C.c_void_p)], C.c_int),
+    ("rl_router_forget", [C.c_void_p, C.POINTER(RlBatch), C.POINTER(C.c_void_p)], C.c_int),
     ("rl_resize", [C.c_void_p, C.POINTER(C.c_uint32)], C.c_int),
     ("rl_rule_stats_add_device", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
     ("rl_rule_stats_read", [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32], C.c_int),
@@ -760,6 +765,21 @@ class Engine:
         self._check(self.lib.rl_peek_device(self.h, C.byref(s), out_ptr), "rl_peek_device")
 
     # ---- rule stats (rl_hip.h "Rule stats") ----
+    def peek_routed(self, rec_ptr: int, n: int, reply_ptr: int, forget: bool = False):
+        """rl_peek_routed: the owner's lookup of n routed records in device memory (ROUTE_RECORD_BYTES
+        each) -> n rl_peek_reply at reply_ptr (device), asynchronous on the engine stream; forget:
+        then the clears over the same records (reply_ptr may be 0)."""
+        self._check(self.lib.rl_peek_routed(self.h, rec_ptr or None, n, reply_ptr or None,
+                                            PEEK_ROUTED_FORGET if forget else 0), "rl_peek_routed")
+
+    def route_unpack_peek(self, n_desc: int, perm_ptr: int, back_ptr: int, out_ptr: int):
+        """rl_route_unpack_peek: out[i] = back[perm[i]] (NIL where perm[i] is ROUTE_LOCAL), all in
+        device memory, asynchronous on the engine stream."""
+        s = RlBatch()
+        s.n_desc, s.n_req, s.blob_bytes, s.reserved = n_desc, 0, 0, 0
+        self._check(self.lib.rl_route_unpack_peek(self.h, C.byref(s), perm_ptr or None, back_ptr or None,
+                                                  out_ptr or None), "rl_route_unpack_peek")
+
     def rule_stats(self, first: int = 0, n: Optional[int] = None, clear: bool = False) -> np.ndarray:
         """rl_rule_stats_read: the stat counters of rule ids [first, first + n) (RULE_STAT_DTYPE;
         n=None: up to the last rule loaded through this object), zeroed afterwards with clear.
@@ -1069,6 +1089,27 @@ class Router:
             if self._keep:
                 self._keep.pop(0)
         return [(outs[i][:nd], thrs[i][:nr]) for i, (nd, nr) in enumerate(sizes)]
+
+    def _peek(self, batches, fn, what):
+        structs = [_batch_struct(b) for b in batches]
+        for s in structs:  # (ignored by the call; staged as zeros)
+            s.hits_addend, s.ttl_jitter = None, None
+        arr = (RlBatch * self.n)(*structs)
+        outs = [np.zeros(max(1, b.n_desc), PEEK_DTYPE) for b in batches]
+        o = (C.c_void_p * self.n)(*[x.ctypes.data for x in outs])
+        self._check(fn(self.h, arr, o), what)
+        return [outs[i][:b.n_desc] for i, b in enumerate(batches)]
+
+    def peek(self, batches) -> list:
+        """rl_router_peek: host Batch per engine passed at create (collective transports: every rank
+        calls, an empty Batch where it asks nothing) -> one PEEK_DTYPE array per batch, each
+        descriptor answered by the owner of its key."""
+        return self._peek(batches, self.lib.rl_router_peek, "rl_router_peek")
+
+    def forget(self, batches) -> list:
+        """rl_router_forget: the same call, clearing at each owner after every lookup of the call;
+        returns the replies as read before the clears."""
+        return self._peek(batches, self.lib.rl_router_forget, "rl_router_forget")
 
     def allgather_host(self, data: bytes, n_ranks: int) -> list:
         """rl_router_allgather_host: every rank's `data` (the same length everywhere), in rank

@@ -694,8 +694,9 @@ int rl_resize(rl_engine* e, const uint32_t log2_slots[4]);
  * calls them between batches) and between rl_restore_begin and rl_restore_end. An open snapshot
  * does not block them: the snapshot is the state at its begin.
  *
- * Out of scope: a routed deployment (each rank's engine answers for the keys it owns; the others
- * read as absent there), and a compact wire form. */
+ * A routed deployment: each rank's engine answers only for the keys it owns (the others read as
+ * absent there), so a router is asked through rl_router_peek / rl_router_forget ("Routed peek /
+ * forget" below), which send every key to its owner. Out of scope: a compact wire form. */
 enum {
   RL_PEEK_FOUND = 1u,
   RL_PEEK_LOCAL_CACHED = 2u,
@@ -713,6 +714,55 @@ typedef struct rl_peek_reply { /* 16 B */
 int rl_peek(rl_engine* e, const rl_batch* host_batch, rl_peek_reply* out);
 int rl_peek_device(rl_engine* e, const rl_batch* device_batch, rl_peek_reply* d_out);
 int rl_forget(rl_engine* e, const rl_batch* host_batch, rl_peek_reply* out_or_null);
+
+/* ---- Routed peek / forget --------------------------------------------------
+ * The same lookups where the keys are spread over the shards of a router.
+ *
+ * Engine level (the pieces a router call is made of; device memory, ordered on the engine
+ * stream, returning at once):
+ * rl_peek_routed: the owner's lookup of n routed records (RL_ROUTE_RECORD_BYTES each, as
+ * rl_route_pack_strided writes them: prefix lanes, request time, rule id), one rl_peek_reply per
+ * record into d_reply. The key string's identity is rebuilt from the record as the owner's decision
+ * path rebuilds it, and from there the lookup is rl_peek_device's own code. A record whose rule id
+ * is at or above the loaded rule count, or whose time is above 0xFFFD0000, gets RL_PEEK_BAD and
+ * zeros. With RL_PEEK_ROUTED_FORGET the lookup pass over all n records is followed by the clearing
+ * pass over the same records (rl_forget's order: every duplicate reports the state before the
+ * call); d_reply may then be NULL. RL_ESTATE while a batch is in flight or a restore is open;
+ * n == 0 launches nothing.
+ * rl_route_unpack_peek: the origin's side. d_out[i] = {0, 0, 0, RL_PEEK_NIL} when d_perm[i] is
+ * RL_ROUTE_LOCAL, else d_back[d_perm[i]]: d_perm as rl_route_pack_strided wrote it, d_back the
+ * owners' replies strided like the send buffer. Reads only n_desc of the batch.
+ *
+ * rl_router_peek / rl_router_forget: host memory in and out, synchronous; one batch and one output
+ * per engine passed at create (local transport: n_shards, collective transports: one).
+ * hits_addend and ttl_jitter are ignored and may be NULL. Collective: every rank makes the call at
+ * the same place in its sequence of router calls; a rank with nothing to ask passes n_desc == 0.
+ * With a step in flight the call returns RL_ESTATE before any collective (by the router's contract
+ * every rank is then in the same state). Each origin packs its batch by owner (one record per
+ * descriptor, no combining), counts and records move as in a step, each owner runs rl_peek_routed
+ * over everything it received (origin-major), the 16-B replies return by the reverse exchange and
+ * the origin unpacks them. A forget's owners run the lookup pass over all received records before
+ * the clearing pass, so every duplicate of a string, across descriptors and across origins of
+ * the call, reports the state before the call.
+ * Refused before anything is staged: rl_peek's list (RL_EINVAL), a rule id at or above 0xFFFF (the
+ * record's rule word shares its upper half; RL_EINVAL), n_desc / n_req over the router's max_desc
+ * or blob_bytes over its max_blob_bytes (RL_ECAPACITY). Such a refusal, a staging or allocation
+ * failure and a pack status travel as this origin's status in the counts exchange, as a step's
+ * pack status does: if any origin's is non-zero no owner looks up or clears anything, every rank
+ * still finishes the counts exchange, the failing rank returns its code (local transport: the
+ * first failing shard's code) and the others RL_EPEER, and out is untouched — a forget is
+ * all-or-nothing across ranks for every failure the call can see before records move. A HIP or
+ * communicator failure after that returns RL_EHIP / RL_EPEER / RL_ECOMM as a step's does, and a
+ * forget may then have been applied at some owners: the per-node atomicity of a Redis cluster DEL
+ * pipeline. The call does not move the step clock, cannot return RL_ELATE, does not touch the hot
+ * sets and leaves rl_router_stats alone. Its two reply buffers (and, without RL_ROUTER_HOST, its
+ * input staging) are allocated at the first call; everything else is a free step slot's. */
+enum { RL_PEEK_ROUTED_FORGET = 1u };
+int rl_peek_routed(rl_engine* e, const void* d_records, uint32_t n, rl_peek_reply* d_reply, uint32_t flags);
+int rl_route_unpack_peek(rl_engine* e, const rl_batch* device_batch, const uint32_t* d_perm,
+                         const rl_peek_reply* d_back, rl_peek_reply* d_out);
+int rl_router_peek(rl_router* r, const rl_batch* host_batches, rl_peek_reply* const* out);
+int rl_router_forget(rl_router* r, const rl_batch* host_batches, rl_peek_reply* const* out_or_null);
 
 /* ---- Rule stats: per-rule stat counters summed on the device ---------------
  * The reference keeps four counters per limit, <FullKey>.total_hits / .over_limit / .near_limit /
