@@ -674,16 +674,50 @@ void HipRateLimitCache::finish(Staged& st) {
           fc_->Set(c.fkey[i], unit_divider(lim->Limit.unit), (uint32_t)c.now);
       }
     }
+    if (!fc_ && s_.local_cache) {
+      // the device cache's lookup counters: one Get per descriptor with a limit
+      // (fixed_cache_impl.go:55-66), a hit where the status says so, before the caller is released
+      uint64_t looks = 0, hits = 0;
+      for (size_t i = 0; i < c.prefix.size(); ++i) {
+        if (!(*c.limits)[i]) continue;
+        ++looks;
+        hits += ((out[d + i].code_flags >> 8) & RL_FLAG_LOCAL_CACHE_HIT) ? 1u : 0u;
+      }
+      lc_lookups_.fetch_add(looks, std::memory_order_relaxed);
+      lc_hits_.fetch_add(hits, std::memory_order_relaxed);
+    }
     answer(c, out + d, thr[r]);
     d += c.prefix.size();
   }
   done_calls(st.calls.size());
 }
 
+// hits, misses, lookups, entries, evicted, expired. HIP_LOCAL_CACHE=freecache: the host model's.
+// The device cache: hits / lookups as finish() counted them; entries / expired from an rl_census
+// at the time source's now, a control call on the submitter thread (as Peek), so every DoLimit
+// enqueued before it is decided first; evicted is 0, the device cache never evicts.
 void HipRateLimitCache::local_cache_stats(uint64_t* out) {
   for (int k = 0; k < 6; ++k) out[k] = 0;
-  std::lock_guard<std::mutex> g(fc_mu_);
-  if (fc_) fc_->stats(out);
+  {
+    std::lock_guard<std::mutex> g(fc_mu_);
+    if (fc_) {
+      fc_->stats(out);
+      return;
+    }
+  }
+  if (!s_.local_cache) return;
+  rl_census_report rep;
+  memset(&rep, 0, sizeof rep);
+  rep.struct_size = sizeof rep;
+  control([this, &rep]() -> std::string { return rl_census(eng_, ts_->UnixNow(), &rep) ? rl_last_error(eng_) : ""; });
+  const uint64_t hits = lc_hits_.load(std::memory_order_relaxed), looks = lc_lookups_.load(std::memory_order_relaxed);
+  out[0] = hits;
+  out[1] = looks - hits;
+  out[2] = looks;
+  for (int r = 0; r < 8; ++r) {
+    out[3] += rep.cached[r];
+    out[5] += rep.cache_expired[r];
+  }
 }
 
 // The submitter thread owns the engine (rl_hip.h: one thread per engine) and keeps two batches

@@ -281,7 +281,11 @@ class HipRateLimitCache : public RateLimitCache {
   }
   // (tests) set before the first DoLimit
   void set_trace(TraceFn f) { trace_ = std::move(f); }
-  // HIP_LOCAL_CACHE=freecache: hits, misses, lookups, entries, evicted, expired (zeros otherwise)
+  // The ratelimit.localcache.* gauges: hits, misses, lookups, entries, evicted,
+  // expired. HIP_LOCAL_CACHE=freecache: the host model's. The device cache: hits / lookups counted
+  // from every answered batch's statuses, entries / expired from an rl_census at the time source's
+  // now (a control call: every DoLimit enqueued before it is decided first), evicted 0. Zeros with
+  // the local cache off.
   void local_cache_stats(uint64_t* out);
 
  private:
@@ -317,6 +321,7 @@ class HipRateLimitCache : public RateLimitCache {
   bool rules_dirty_ = false;
   std::atomic<uint64_t> n_batches_{0}, n_loads_{0}, n_loads_inflight_{0}, n_drains_{0}, n_compact_{0};
   std::atomic<uint64_t> n_resizes_{0}, n_resize_fail_{0};
+  std::atomic<uint64_t> lc_lookups_{0}, lc_hits_{0};  // the device cache's Gets and hits (finish())
   uint32_t grow_failed_at_[4] = {0, 0, 0, 0};  // live slots of the unit when its last grow failed (0 = none)
   // statuses of a compact batch made on the host from its raw replies (rl_decide_raw)
   std::vector<rl_status> dec_out_;

@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "rl_census.h"
 #include "rl_common.h"
 #include "rl_hip.h"
 #include "rl_internal.h"
@@ -90,12 +91,12 @@ namespace {
 
 enum KernelId {
   KT_FINGERPRINT, KT_HISTOGRAM, KT_HIST_SCAN, KT_SORT_PASS, KT_SCAN, KT_LEADER, KT_DECIDE, KT_FALLBACK, KT_MEMSET,
-  KT_CAND, KT_V4_HIST, KT_V4_SCAN, KT_V4_PLACE, KT_V4_GROUP, KT_RESOLVE, KT_RULE_STATS, KT_COUNT
+  KT_CAND, KT_V4_HIST, KT_V4_SCAN, KT_V4_PLACE, KT_V4_GROUP, KT_RESOLVE, KT_RULE_STATS, KT_CACHE_STATS, KT_CENSUS, KT_COUNT
 };
 const char* const kKernelNames[KT_COUNT] = {"k_fingerprint", "k_histogram", "k_hist_scan", "k_sort_pass", "k_scan",
                                             "k_leader",      "k_decide",    "fallback",    "memset",      "k_cand_state",
                                             "k4_hist",       "k4_scan",     "k4_place",    "k4_group",
-                                            "k_resolve",     "k_rule_stats"};
+                                            "k_resolve",     "k_rule_stats", "k_cache_stats", "k_census"};
 
 enum Mode { MODE_LSD = 1, MODE_LSD_FULL = 2, MODE_V4 = 4 };
 
@@ -150,8 +151,22 @@ struct rl_engine {
   int rs_variant = 0;                // 0: sums of low rule ids in LDS; 1: global adds only (RL_DIAG_RULE_STATS_VARIANT)
   uint32_t rs_blocks = 256;          // k_rule_stats' persistent grid (RL_DIAG_RULE_STATS_BLOCKS)
   int rstats_ensure();
-  int count_batch(const rl_batch& b, const rl_status* out, const EngineCtl* ctl);
-  bool counts(const rl_batch& b) const { return (cfg.flags & RL_CFG_RULE_STATS) && !b.reserved && b.n_desc; }
+  // local-cache lookup counters and the census' control block (rl_hip.h "Local-cache gauges"):
+  // allocated at first use and kept
+  CacheStatCtl* d_cstats = nullptr;
+  uint32_t cs_blocks = 256;          // k_cache_stats' persistent grid (RL_DIAG_CACHE_STATS_BLOCKS)
+  CensusCtl* d_census = nullptr;
+  CensusCtl* h_census = nullptr;     // pinned
+  uint32_t census_blocks = 1024;     // k_census' grid bound (RL_DIAG_CENSUS_BLOCKS)
+  int cstats_ensure();
+  // what is folded in behind a batch: COUNT_RULE (k_rule_stats) | COUNT_CACHE (k_cache_stats)
+  enum : uint32_t { COUNT_RULE = 1u, COUNT_CACHE = 2u };
+  int count_batch(const rl_batch& b, const rl_status* out, const EngineCtl* ctl, uint32_t which);
+  uint32_t counts(const rl_batch& b) const {
+    if (b.reserved || !b.n_desc) return 0u;
+    return ((cfg.flags & RL_CFG_RULE_STATS) ? (uint32_t)COUNT_RULE : 0u) |
+           ((cfg.flags & RL_CFG_CACHE_STATS) && cfg.local_cache ? (uint32_t)COUNT_CACHE : 0u);
+  }
   // the control block run_pipeline gives the batch it is about to run in `mode`
   const EngineCtl* batch_ctl(int mode) const {
     return mode == MODE_V4 ? v4_ctl[sub_seq % 3] : reinterpret_cast<const EngineCtl*>(zero_block);
@@ -320,7 +335,7 @@ struct rl_engine {
     rl_status* user_out = nullptr; // host batch: rl_wait copies here (may be null)
     uint32_t* user_thr = nullptr;
     bool poll = false;             // completion = k4_group's done word behind h_ctl (no event)
-    bool count = false;            // RL_CFG_RULE_STATS: k_rule_stats runs behind the batch's pipeline
+    uint32_t count = 0;            // COUNT_*: k_rule_stats / k_cache_stats run behind the batch's pipeline
   };
   Flight fl[HSLOTS];
   // A device v4 batch completes on the word k4_group's last block writes behind the slot's pinned
@@ -747,12 +762,45 @@ int rl_engine::rstats_ensure() {
   return 0;
 }
 
-int rl_engine::count_batch(const rl_batch& b, const rl_status* out, const EngineCtl* ctl) {
-  int rc = rstats_ensure();
-  if (rc) return rc;
-  timed(KT_RULE_STATS, [&] { launch_rule_stats(stream, b, out, n_rules, d_rstats, ctl, rs_variant, rs_blocks); });
-  const hipError_t he = hipGetLastError();
-  return he == hipSuccess ? 0 : hip_fail(he, "k_rule_stats launch");
+// The lookup counters, zeroed at their allocation.
+int rl_engine::cstats_ensure() {
+  if (d_cstats) return 0;
+  if (!d_rules) {
+    int rc = rl_load_rules(this, nullptr, 0);
+    if (rc) return rc;
+  }
+  CacheStatCtl* nt = nullptr;
+  hipError_t he = hipMalloc(&nt, sizeof(CacheStatCtl));
+  if (he != hipSuccess) {
+    (void)hipGetLastError();
+    return hip_fail(he, "hipMalloc(cache stats)");
+  }
+  he = hipMemsetAsync(nt, 0, sizeof(CacheStatCtl), stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(stream);
+  if (he != hipSuccess) {
+    hipFree(nt);
+    return hip_fail(he, "cache stats allocation");
+  }
+  d_cstats = nt;
+  return 0;
+}
+
+int rl_engine::count_batch(const rl_batch& b, const rl_status* out, const EngineCtl* ctl, uint32_t which) {
+  if (which & COUNT_RULE) {
+    int rc = rstats_ensure();
+    if (rc) return rc;
+    timed(KT_RULE_STATS, [&] { launch_rule_stats(stream, b, out, n_rules, d_rstats, ctl, rs_variant, rs_blocks); });
+    const hipError_t he = hipGetLastError();
+    if (he != hipSuccess) return hip_fail(he, "k_rule_stats launch");
+  }
+  if (which & COUNT_CACHE) {
+    int rc = cstats_ensure();
+    if (rc) return rc;
+    timed(KT_CACHE_STATS, [&] { launch_cache_stats(stream, b, out, n_rules, d_cstats, ctl, cs_blocks); });
+    const hipError_t he = hipGetLastError();
+    if (he != hipSuccess) return hip_fail(he, "k_cache_stats launch");
+  }
+  return 0;
 }
 
 int rl_engine::enqueue_d2h(const Flight& f, hipStream_t s) {
@@ -797,9 +845,9 @@ int rl_engine::settle(Flight& f) {
     st.inserted_keys += h_ctl->n_inserted;
     int rc = run_pipeline(f.b, f.out, f.thr, MODE_LSD, nullptr, true);
     if (rc) return rc;
-    // (the first attempt's k_rule_stats saw its error word and counted nothing; this one sees
+    // (the first attempt's counting kernels saw its error word and counted nothing; these see
     // the rerun's: a rerun that asks for a re-sort is counted behind that)
-    if (f.count && (rc = count_batch(f.b, f.out, batch_ctl(MODE_LSD))) != 0) return rc;
+    if (f.count && (rc = count_batch(f.b, f.out, batch_ctl(MODE_LSD), f.count)) != 0) return rc;
     if (f.reply) launch_route_reply(stream, f.b.n_desc, f.out, f.thr, f.reply);
     if (f.host && (rc = enqueue_d2h(f, stream)) != 0) return rc;
     e = hipStreamSynchronize(stream);
@@ -812,7 +860,7 @@ int rl_engine::settle(Flight& f) {
     ++st.resorts;
     int rc = run_pipeline(f.b, f.out, f.thr, MODE_LSD_FULL, nullptr, true);
     if (rc) return rc;
-    if (f.count && (rc = count_batch(f.b, f.out, batch_ctl(MODE_LSD_FULL))) != 0) return rc;
+    if (f.count && (rc = count_batch(f.b, f.out, batch_ctl(MODE_LSD_FULL), f.count)) != 0) return rc;
     if (f.reply) launch_route_reply(stream, f.b.n_desc, f.out, f.thr, f.reply);
     if (f.host && (rc = enqueue_d2h(f, stream)) != 0) return rc;
     e = hipStreamSynchronize(stream);
@@ -931,13 +979,13 @@ int rl_engine::submit_common(const rl_batch& d, rl_status* out, uint32_t* thr, R
   if (rc) return rc;
   if (reply) launch_route_reply(stream, d.n_desc, out, thr, reply);
   Flight f;
-  // Rule stats from the final statuses, right behind the pipeline: the batch's control block is
+  // Rule stats and lookup counters from the final statuses, right behind the pipeline: the batch's control block is
   // complete there (every kernel that writes its error word is ahead on the stream, k4_hist
   // through the front stream's join) and is cleared only by the next batch's pipeline, behind
   // this launch (k4_group clears the block of the batch two after its own; the LSD block is
   // zeroed at the start of the next LSD run).
   f.count = counts(d);
-  if (f.count && (rc = count_batch(d, out, batch_ctl(default_mode()))) != 0) return rc;
+  if (f.count && (rc = count_batch(d, out, batch_ctl(default_mode()), f.count)) != 0) return rc;
   f.b = d;
   f.out = out;
   f.thr = thr;
@@ -961,7 +1009,7 @@ int rl_engine::submit_common(const rl_batch& d, rl_status* out, uint32_t* thr, R
     // outputs stay in device memory; the host summary was written with a system-scope
     // release by k4_group (or copied by the LSD path's own D2H copy, ordered before this)
     const bool dev_only = default_mode() == MODE_V4 && !reply && d.n_desc;
-    // (a counted batch completes on an event behind k_rule_stats, which still reads its arrays
+    // (a counted batch completes on an event behind its counting kernels, which still read its arrays
     // after k4_group's done word)
     if (dev_only && !timing && !f.count) {
       f.poll = true;  // k4_group writes the done word (cleared at this submit's start)
@@ -1051,6 +1099,10 @@ int rl_create(const rl_config* cfg_in, rl_engine** out) {
   if (const char* v = getenv("RL_DIAG_RULE_STATS_VARIANT")) e->rs_variant = atoi(v) == 1 ? 1 : 0;  // diagnostics (A/B)
   if (const char* v = getenv("RL_DIAG_RULE_STATS_BLOCKS"))
     e->rs_blocks = std::min<uint32_t>(std::max<uint32_t>((uint32_t)strtoul(v, nullptr, 10), 1u), 1024u);
+  if (const char* v = getenv("RL_DIAG_CACHE_STATS_BLOCKS"))
+    e->cs_blocks = std::min<uint32_t>(std::max<uint32_t>((uint32_t)strtoul(v, nullptr, 10), 1u), 1024u);
+  if (const char* v = getenv("RL_DIAG_CENSUS_BLOCKS"))
+    e->census_blocks = std::min<uint32_t>(std::max<uint32_t>((uint32_t)strtoul(v, nullptr, 10), 1u), 1024u);
   e->lo_bit = 64 - (int)c.sort_bits;
   hipError_t he = hipSetDevice(c.device);
   if (he != hipSuccess) {
@@ -1229,7 +1281,7 @@ void rl_destroy(rl_engine* e) {
   for (void* p : {(void*)e->v4_hoff, (void*)e->v4_dfr, (void*)e->v4_hb,
                   e->v4_scratch, (void*)e->d_poison, (void*)e->d_tree_nodes,
                   (void*)e->d_tree_slots, (void*)e->d_tree_names, (void*)e->d_tree_fnodes, (void*)e->d_tree_fslots, (void*)e->d_res, (void*)e->d_res_flags, (void*)e->table, (void*)e->d_occ,
-                  (void*)e->d_rules, (void*)e->d_rstats, (void*)e->keys_orig, (void*)e->keys_a, (void*)e->keys_b, (void*)e->vals_a,
+                  (void*)e->d_rules, (void*)e->d_rstats, (void*)e->d_cstats, (void*)e->d_census, (void*)e->keys_orig, (void*)e->keys_a, (void*)e->keys_b, (void*)e->vals_a,
                   (void*)e->vals_b, (void*)e->recs, (void*)e->srec, (void*)e->seg, (void*)e->offs,
                   (void*)e->hist_part, (void*)e->fp_part, (void*)e->fp_part2, (void*)e->tile_heads,
                   (void*)e->zero_block, (void*)e->d_cand, (void*)e->r_tmp, (void*)e->r_own, (void*)e->r_bcnt,
@@ -1237,6 +1289,7 @@ void rl_destroy(rl_engine* e) {
     hipFree(p);
   hipHostFree(e->h_hot_stage);
   hipHostFree(e->h_route);
+  hipHostFree(e->h_census);
   for (hipStream_t s : {e->front, e->xin, e->xout, e->own_stream})
     if (s) hipStreamDestroy(s);
   delete e;
@@ -2283,7 +2336,7 @@ int rl_rule_stats_add_device(rl_engine* e, const rl_batch* b, const rl_status* d
   if (b->n_desc && (!b->rule_id || !b->req_of || !b->hits_addend || !d_out))
     return e->fail(RL_EINVAL, "rl_rule_stats_add_device: null rule_id / req_of / hits_addend / status array");
   if (!b->n_desc) return 0;
-  return e->count_batch(*b, d_out, nullptr);
+  return e->count_batch(*b, d_out, nullptr, rl_engine::COUNT_RULE);
 }
 
 int rl_rule_stats_read(rl_engine* e, uint32_t first_rule, uint32_t n, rl_rule_stat* out, uint32_t flags) {
@@ -2305,6 +2358,86 @@ int rl_rule_stats_read(rl_engine* e, uint32_t first_rule, uint32_t n, rl_rule_st
     he = hipMemsetAsync(e->d_rstats + first_rule, 0, bytes, e->stream);
   if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
   return he == hipSuccess ? 0 : e->hip_fail(he, "rl_rule_stats_read");
+}
+
+// ---- Local-cache gauges and the census ----------------------------------------------------
+int rl_cache_stats_add_device(rl_engine* e, const rl_batch* b, const rl_status* d_out) {
+  if (!e || !b) return RL_EINVAL;
+  if (b->reserved) return e->fail(RL_EINVAL, "rl_batch.reserved must be 0");
+  if (b->n_desc > (1u << 30)) return e->fail(RL_EINVAL, "rl_cache_stats_add_device: more than 2^30 descriptors");
+  if (b->n_desc && (!b->rule_id || !d_out))
+    return e->fail(RL_EINVAL, "rl_cache_stats_add_device: null rule_id / status array");
+  if (!b->n_desc || !e->cfg.local_cache) return 0;  // a nil cache gets no lookup
+  return e->count_batch(*b, d_out, nullptr, rl_engine::COUNT_CACHE);
+}
+
+int rl_cache_stats_read(rl_engine* e, rl_cache_stats* out, uint32_t flags) {
+  if (!e) return RL_EINVAL;
+  if (e->n_fl) return e->fail(RL_ESTATE, "rl_cache_stats_read while a batch is in flight (call rl_wait)");
+  if (e->restoring) return e->fail(RL_ESTATE, "rl_cache_stats_read between rl_restore_begin and rl_restore_end");
+  if (flags & ~(uint32_t)RL_CACHE_STATS_CLEAR) return e->fail(RL_EINVAL, "unknown rl_cache_stats_read flags 0x%x", flags);
+  if (!out) return e->fail(RL_EINVAL, "rl_cache_stats_read: null output");
+  memset(out, 0, sizeof *out);
+  if (!e->d_cstats) return 0;  // nothing was ever counted
+  // behind every k_cache_stats queued on the engine stream, the explicit calls' included
+  CacheStatCtl h;
+  hipError_t he = hipMemcpyAsync(&h, e->d_cstats, sizeof h, hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess && (flags & RL_CACHE_STATS_CLEAR)) he = hipMemsetAsync(e->d_cstats, 0, sizeof h, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  if (he != hipSuccess) return e->hip_fail(he, "rl_cache_stats_read");
+  out->lookups = h.w[0][0];
+  out->hits = h.w[1][0];
+  out->misses = out->lookups - out->hits;
+  return 0;
+}
+
+int rl_census(rl_engine* e, int64_t now, rl_census_report* out) {
+  if (!e || !out) return RL_EINVAL;
+  if (out->struct_size != sizeof(rl_census_report))
+    return e->fail(RL_EINVAL, "rl_census: struct_size %u, expected %zu", out->struct_size, sizeof(rl_census_report));
+  if (now < 0 || now > MAX_NOW) return e->fail(RL_EINVAL, "rl_census: time %lld outside [0, 0xFFFD0000]", (long long)now);
+  if (e->n_fl) return e->fail(RL_ESTATE, "rl_census while a batch is in flight (call rl_wait)");
+  if (e->restoring) return e->fail(RL_ESTATE, "rl_census between rl_restore_begin and rl_restore_end");
+  hipError_t he = hipSuccess;
+  if (!e->d_census) {
+    he = hipMalloc(&e->d_census, sizeof(CensusCtl));
+    if (he == hipSuccess) he = hipHostMalloc(&e->h_census, sizeof(CensusCtl), hipHostMallocDefault);
+    if (he != hipSuccess) {
+      (void)hipGetLastError();
+      hipFree(e->d_census);
+      e->d_census = nullptr;
+      return e->hip_fail(he, "census control allocation");
+    }
+  }
+  SnapGens g;
+  for (int r = 0; r < 8; ++r) g.gen[r] = e->occ[r].gen;  // nothing is in flight: the mirror's are the table's
+  he = hipMemsetAsync(e->d_census, 0, sizeof(CensusCtl), e->stream);
+  if (he == hipSuccess) {
+    e->timed(KT_CENSUS, [&] {
+      launch_census(e->stream, e->tab, e->table_slots, g, (uint32_t)now, e->d_census, e->census_blocks);
+    });
+    he = hipGetLastError();
+  }
+  if (he == hipSuccess) he = hipMemcpyAsync(e->h_census, e->d_census, sizeof(CensusCtl), hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  if (he != hipSuccess) return e->hip_fail(he, "rl_census");
+  rl_census_report rep;
+  memset(&rep, 0, sizeof rep);
+  rep.struct_size = sizeof rep;
+  for (int r = 0; r < 8; ++r) {
+    const unsigned long long(*w)[32] = e->h_census->w + r * CENSUS_FIELDS;
+    rep.slots[r] = 1ull << e->tab.region_log2[r];
+    rep.live[r] = w[CF_LIVE][0];
+    rep.prev[r] = w[CF_PREV][0];
+    rep.stale[r] = w[CF_STALE][0];
+    rep.keys_main[r] = w[CF_MAIN][0];
+    rep.keys_per_second[r] = w[CF_PS][0];
+    rep.cached[r] = w[CF_CACHED][0];
+    rep.cache_expired[r] = w[CF_EXPIRED][0];
+  }
+  for (int k = 0; k < RL_CENSUS_LOG2_BINS; ++k) rep.count_log2[k] = e->h_census->w[CENSUS_HIST0 + k][0];
+  *out = rep;
+  return 0;
 }
 
 int rl_set_timing(rl_engine* e, int on) {

@@ -34,6 +34,31 @@ enum : uint32_t {
   SNAP_ERR_DUP = 8u,       // import: the identity (claim word, key) occurs twice
 };
 
+// What every streaming table pass shares (k_snap_export, k_rehash, rl_census.hip k_census).
+namespace snap {
+// Region of a table slot index, and that region's newest generation, by select chains over
+// constant indices (the by-value arguments stay in scalar registers, rl_decide.h region_geom).
+__device__ __forceinline__ uint32_t region_of_slot(const TableDesc& tab, uint64_t i) {
+  uint32_t r = 0;
+#pragma unroll
+  for (int k = 1; k < 8; ++k) r += i >= tab.region_base[k] ? 1u : 0u;
+  return r;
+}
+__device__ __forceinline__ uint32_t gen_of_region(const SnapGens& g, uint32_t region) {
+  uint32_t v = g.gen[0];
+#pragma unroll
+  for (int k = 1; k < 8; ++k) v = region == (uint32_t)k ? g.gen[k] : v;
+  return v;
+}
+// Generation class of a slot of generation g in a region whose newest generation is G:
+// 0 = the newest, 1 = a lag region's previous one (G - 2), 2 = not live (rl_hip.h "What is live").
+__device__ __forceinline__ uint32_t gen_class(uint32_t g, uint32_t G, bool lazy) {
+  if (g == 0u) return 2u;
+  if (g == G) return 0u;
+  return lazy && g + 2u == G ? 1u : 2u;
+}
+}  // namespace snap
+
 void launch_snap_export(hipStream_t st, const TableDesc& tab, uint64_t n_slots, const SnapGens& gens, Slot* out,
                         uint64_t cap, SnapCtl* ctl);
 // Import n records (device memory), then check the chunk for duplicate identities.

@@ -22,28 +22,6 @@ constexpr int TILE = NT * PER;           // slots per reservation
 constexpr int NW = NT / 64;
 static_assert(TILE >= 4096, "one returning atomic per >= 4096 slots");
 
-// Region of a table slot index, and that region's newest generation, by select chains over
-// constant indices (the by-value arguments stay in scalar registers, rl_decide.h region_geom).
-RL_DEV uint32_t region_of_slot(const TableDesc& tab, uint64_t i) {
-  uint32_t r = 0;
-#pragma unroll
-  for (int k = 1; k < 8; ++k) r += i >= tab.region_base[k] ? 1u : 0u;
-  return r;
-}
-RL_DEV uint32_t gen_of_region(const SnapGens& g, uint32_t region) {
-  uint32_t v = g.gen[0];
-#pragma unroll
-  for (int k = 1; k < 8; ++k) v = region == (uint32_t)k ? g.gen[k] : v;
-  return v;
-}
-// Generation class of a slot of generation g in a region whose newest generation is G:
-// 0 = the newest, 1 = a lag region's previous one (G - 2), 2 = not live (rl_hip.h "What is live").
-RL_DEV uint32_t gen_class(uint32_t g, uint32_t G, bool lazy) {
-  if (g == 0u) return 2u;
-  if (g == G) return 0u;
-  return lazy && g + 2u == G ? 1u : 2u;
-}
-
 // Export. A block takes tiles of TILE consecutive slots (grid-stride): every lane reads PER
 // slots (two 16-B loads each, all issued before the first use), the live ones are counted per
 // wave by ballot, the tile's total takes ONE reservation on the output cursor, and every live

@@ -42,6 +42,7 @@ STATUS_DTYPE = np.dtype([("code_flags", "<u4"), ("limit_remaining", "<u4"), ("re
 PIPELINE_FLAGS = {"v4": 0, "lsd": 1}  # rl_config.flags (RL_CFG_LSD_ONLY)
 CFG_LAG_WINDOW = 2  # RL_CFG_LAG_WINDOW: SECOND key strings findable 3 s behind (routers' engines)
 CFG_RULE_STATS = 4  # RL_CFG_RULE_STATS: every completed batch is added to the per-rule stat counters
+CFG_CACHE_STATS = 8  # RL_CFG_CACHE_STATS: every completed batch is added to the local-cache lookup counters
 ABI_VERSION = 7
 
 
@@ -124,6 +125,23 @@ PEEK_ROUTED_FORGET = 1  # RL_PEEK_ROUTED_FORGET: rl_peek_routed clears after it 
 RULE_STATS_CLEAR = 1  # RL_RULE_STATS_CLEAR
 RULE_STAT_FIELDS = ("total_hits", "over_limit", "near_limit", "over_limit_with_local_cache", "shadow_mode")
 RULE_STAT_DTYPE = np.dtype([(f, "<u8") for f in RULE_STAT_FIELDS] + [("reserved", "<u8", (3,))])  # rl_rule_stat, 64 B
+
+
+# ---- local-cache gauges and the census (rl_hip.h "Local-cache gauges and the table census") ----
+CACHE_STATS_CLEAR = 1  # RL_CACHE_STATS_CLEAR
+CACHE_STAT_FIELDS = ("hits", "misses", "lookups")
+CENSUS_LOG2_BINS = 33  # RL_CENSUS_LOG2_BINS
+CENSUS_REGION_FIELDS = ("slots", "live", "prev", "stale", "keys_main", "keys_per_second", "cached", "cache_expired")
+
+
+class RlCacheStats(C.Structure):
+    _fields_ = [("hits", C.c_uint64), ("misses", C.c_uint64), ("lookups", C.c_uint64), ("reserved", C.c_uint64 * 5)]
+
+
+class RlCensusReport(C.Structure):
+    _fields_ = ([("struct_size", C.c_uint32), ("reserved0", C.c_uint32)] +
+                [(f, C.c_uint64 * 8) for f in CENSUS_REGION_FIELDS] +
+                [("count_log2", C.c_uint64 * CENSUS_LOG2_BINS), ("reserved", C.c_uint64 * 6)])
 
 
 # ---- snapshot / restore (rl_hip.h "Snapshot / restore") ----
@@ -282,6 +300,9 @@ ABI = [
     ("rl_resize", [C.c_void_p, C.POINTER(C.c_uint32)], C.c_int),
     ("rl_rule_stats_add_device", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
     ("rl_rule_stats_read", [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32], C.c_int),
+    ("rl_cache_stats_add_device", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
+    ("rl_cache_stats_read", [C.c_void_p, C.POINTER(RlCacheStats), C.c_uint32], C.c_int),
+    ("rl_census", [C.c_void_p, C.c_int64, C.POINTER(RlCensusReport)], C.c_int),
 ]
 
 # multi-GPU router record sizes (include/rl_hip.h RL_ROUTE_*)
@@ -484,7 +505,7 @@ class Engine:
                  max_batch_req: Optional[int] = None, max_blob_bytes: Optional[int] = None, sort_bits: int = 48,
                  hash_seed: int = 0x5EE7AB1E5EED, lib_path: Optional[os.PathLike] = None, lsd_only: bool = False,
                  pipeline: str = "v4", max_load_permille: int = 0, lag_window: bool = False,
-                 rule_stats: bool = False):
+                 rule_stats: bool = False, cache_stats: bool = False):
         """pipeline: "v4" (default: tile-sorted records, hot keys decided in place, MSD buckets
         gathered and grouped in LDS) or "lsd" (radix-sort pipeline, also v4's fallback).
         lsd_only=True is pipeline="lsd". log2_slots: table slots per window generation for the
@@ -507,7 +528,7 @@ class Engine:
         cfg.max_blob_bytes = max_blob_bytes or max_batch_desc * 64
         cfg.sort_bits = sort_bits
         cfg.flags = (PIPELINE_FLAGS[pipeline] | (CFG_LAG_WINDOW if lag_window else 0) |
-                     (CFG_RULE_STATS if rule_stats else 0))
+                     (CFG_RULE_STATS if rule_stats else 0) | (CFG_CACHE_STATS if cache_stats else 0))
         cfg.hash_seed = hash_seed
         cfg.max_load_permille = max_load_permille
         self.cfg = cfg
@@ -800,6 +821,35 @@ class Engine:
         s.n_desc, s.n_req, s.blob_bytes, s.reserved = n_desc, n_req, blob_bytes, 0
         _set_ptrs(s, ptrs)
         self._check(self.lib.rl_rule_stats_add_device(self.h, C.byref(s), out_ptr), "rl_rule_stats_add_device")
+
+    # ---- local-cache gauges and the census (rl_hip.h "Local-cache gauges and the table census") ----
+    def cache_stats(self, clear: bool = False) -> dict:
+        """rl_cache_stats_read: {"hits", "misses", "lookups"} of the local over-limit cache, zeroed
+        afterwards with clear. Needs nothing in flight; all 0 on an engine without the cache."""
+        out = RlCacheStats()
+        self._check(self.lib.rl_cache_stats_read(self.h, C.byref(out), CACHE_STATS_CLEAR if clear else 0),
+                    "rl_cache_stats_read")
+        return {f: int(getattr(out, f)) for f in CACHE_STAT_FIELDS}
+
+    def cache_stats_add_device(self, n_desc: int, n_req: int, blob_bytes: int, ptrs, out_ptr: int):
+        """rl_cache_stats_add_device: add the statuses at out_ptr (device memory, n_desc rl_status) of
+        an rl_batch of device pointers (ptrs = blob, off, rule, req_of, now, hits; only rule is
+        read, the others may be 0) to the lookup counters, asynchronous on the engine stream."""
+        s = RlBatch()
+        s.n_desc, s.n_req, s.blob_bytes, s.reserved = n_desc, n_req, blob_bytes, 0
+        _set_ptrs(s, ptrs)
+        self._check(self.lib.rl_cache_stats_add_device(self.h, C.byref(s), out_ptr), "rl_cache_stats_add_device")
+
+    def census(self, now: int) -> dict:
+        """rl_census: one read-only pass over the counter table at time `now`. Per-region uint64
+        arrays (8 entries: slots, live, prev, stale, keys_main, keys_per_second, cached,
+        cache_expired) and count_log2 (33 entries). Needs nothing in flight."""
+        rep = RlCensusReport()
+        rep.struct_size = C.sizeof(RlCensusReport)
+        self._check(self.lib.rl_census(self.h, now, C.byref(rep)), "rl_census")
+        out = {f: np.array(getattr(rep, f), np.uint64) for f in CENSUS_REGION_FIELDS}
+        out["count_log2"] = np.array(rep.count_log2, np.uint64)
+        return out
 
     # ---- snapshot / restore (rl_hip.h "Snapshot / restore") ----
     def snapshot_begin(self) -> RlSnapshotHeader:

@@ -91,8 +91,11 @@ enum {
                             table has seen, at up to twice the SECOND regions' live slots against the same load
                             limit. rl_router_create turns it on for its engines (origins' clocks differ); a lone
                             engine fed in enqueue order does not need it */
-  RL_CFG_RULE_STATS = 4u /* add every completed batch's stat increments to the per-rule counters on the device
+  RL_CFG_RULE_STATS = 4u,/* add every completed batch's stat increments to the per-rule counters on the device
                             ("Rule stats" below) */
+  RL_CFG_CACHE_STATS = 8u /* add every completed batch's local-cache lookups and hits to the lookup counters on
+                            the device ("Local-cache gauges" below); nothing is counted or launched with
+                            local_cache == 0 */
 };
 
 /* One rate-limit rule: config.RateLimit.Limit (src/config/config.go:26-32). */
@@ -806,8 +809,8 @@ int rl_router_forget(rl_router* r, const rl_batch* host_batches, rl_peek_reply* 
  * state: rl_reset, restore and rl_resize leave them alone, only RL_RULE_STATS_CLEAR zeroes them.
  * Rows are per rule id, so a caller that replaces rules (an id changes its meaning) reads and
  * clears first. Out of scope: HipRateLimitCache (its ids name (limit, unit, shadow), not a stats
- * key, and it walks every status on the host anyway), counting inside rl_router_step, and
- * freecache's gauges. */
+ * key, and it walks every status on the host anyway) and counting inside rl_router_step.
+ * (freecache's gauges have their own section, "Local-cache gauges" below.) */
 typedef struct rl_rule_stat {     /* 64 B, one per rule id */
   uint64_t total_hits;                  /* += max(1, hits_addend) per descriptor of the rule */
   uint64_t over_limit;                  /* += over_limit_delta */
@@ -819,6 +822,73 @@ typedef struct rl_rule_stat {     /* 64 B, one per rule id */
 enum { RL_RULE_STATS_CLEAR = 1u };
 int rl_rule_stats_add_device(rl_engine* e, const rl_batch* device_batch, const rl_status* d_out);
 int rl_rule_stats_read(rl_engine* e, uint32_t first_rule, uint32_t n, rl_rule_stat* out, uint32_t flags);
+
+/* ---- Local-cache gauges and the table census --------------------------------
+ * The reference publishes eight ratelimit.localcache.* gauges from freecache
+ * (src/limiter/local_cache_stats.go:20-43). The device's local over-limit cache is the frz word
+ * of a key string's table slot, so its gauges come from two places: lookup counters a kernel adds
+ * to behind each batch (hitCount, missCount, lookupCount), and a census of the table (entryCount,
+ * expiredCount). evacuateCount, overwriteCount and averageAccessTime are 0: the device cache
+ * never evicts (parity unpinned there).
+ *
+ * Lookup counters. The reference makes one freecache Get per descriptor with a limit
+ * (fixed_cache_impl.go:55-66). Contribution of descriptor i: nothing when rule_id[i] is
+ * RL_NIL_RULE or at or above the loaded rule count; otherwise lookups += 1, and hits += 1 when
+ * its status carries RL_FLAG_LOCAL_CACHE_HIT. misses = lookups - hits, computed at the read.
+ * With rl_config.local_cache == 0 nothing is counted and nothing is launched (the reference
+ * makes no Get with a nil cache), and the read returns zeros.
+ *
+ * rl_cache_stats_add_device folds the statuses d_out[n_desc] of one device batch in. It reads
+ * n_desc, rule_id and the statuses' code_flags (the other arrays may be NULL; n_desc <= 2^30), is
+ * ordered on the engine stream, returns at once and is legal with batches in flight. A routed
+ * origin calls it on the statuses rl_route_unpack left in device memory.
+ * RL_CFG_CACHE_STATS makes it automatic under RL_CFG_RULE_STATS' rules, word for word: every
+ * batch completed through rl_submit, rl_submit_device or rl_submit_pipelined is folded in exactly
+ * once from its final statuses, reruns and LSD fallbacks included; a batch whose rl_wait returns
+ * an error adds nothing; the raw forms and rl_submit_routed are not counted at the owner. With
+ * both flags set both kernels run and the batch completes behind the last.
+ * rl_cache_stats_read synchronises the engine stream and copies the counters out; with
+ * RL_CACHE_STATS_CLEAR it zeroes them afterwards. RL_ESTATE while a batch is in flight or a
+ * restore is open. rl_reset, restore and rl_resize leave the counters alone.
+ *
+ * rl_census: one read-only streaming pass over the counter table, evaluated per slot with the
+ * predicates rl_peek applies per key, at the time `now`. It writes nothing to the table, the
+ * occupancy, the hot set or any stat. live[] / prev[] are exact and equal what an
+ * rl_snapshot_begin at the same moment puts in its header ("What is live" above); the occupancy
+ * of rl_get_occupancy may over-count. RL_ESTATE while a batch is in flight or a restore is open
+ * (the rl_peek rule); an open snapshot does not block it. RL_EINVAL for now outside
+ * [0, 0xFFFD0000] or a wrong struct_size. Legal on a router's engine between steps: each rank
+ * reports its shard.
+ * One limit: the census counts slots. For a `now` older than the table's newest request time, or
+ * with EXPIRE jitter, Redis may still hold keys whose slots are no longer live (their window
+ * generation was superseded); those are not counted. */
+typedef struct rl_cache_stats {  /* 64 B */
+  uint64_t hits;        /* ratelimit.localcache.hitCount */
+  uint64_t misses;      /* ratelimit.localcache.missCount = lookups - hits */
+  uint64_t lookups;     /* ratelimit.localcache.lookupCount */
+  uint64_t reserved[5]; /* 0 */
+} rl_cache_stats;
+enum { RL_CACHE_STATS_CLEAR = 1u };
+int rl_cache_stats_add_device(rl_engine* e, const rl_batch* device_batch, const rl_status* d_out);
+int rl_cache_stats_read(rl_engine* e, rl_cache_stats* out, uint32_t flags);
+
+#define RL_CENSUS_LOG2_BINS 33
+typedef struct rl_census_report {       /* 832 B; per region r = (home unit - 1) * 2 + window parity */
+  uint32_t struct_size;                 /* in: = sizeof(rl_census_report) */
+  uint32_t reserved0;                   /* 0 */
+  uint64_t slots[8];                    /* the region's size */
+  uint64_t live[8];                     /* slots of the region's newest window generation */
+  uint64_t prev[8];                     /* slots of generation gen - 2 (lag regions; else 0) */
+  uint64_t stale[8];                    /* claimed slots (generation != 0) that are not live: reusable */
+  uint64_t keys_main[8];                /* live-or-prev slots with now < expiry: what GET on the main store finds */
+  uint64_t keys_per_second[8];          /* live-or-prev slots with a non-zero per-second counter */
+  uint64_t cached[8];                   /* local_cache on: live-or-prev slots with now < the local-cache
+                                           deadline (entryCount: what a lookup at `now` would hit); else 0 */
+  uint64_t cache_expired[8];            /* local_cache on: the same slots with 0 < deadline <= now */
+  uint64_t count_log2[RL_CENSUS_LOG2_BINS]; /* over the slots counted in keys_main: bit length of the counter */
+  uint64_t reserved[6];                 /* 0 */
+} rl_census_report;
+int rl_census(rl_engine* e, int64_t now, rl_census_report* out);
 
 /* ---- Descriptor-tree resolution (GetLimit) ------------------------
  * Replaces rateLimitConfigImpl.GetLimit (src/config/config_impl.go:274-323) per descriptor,
