@@ -340,12 +340,15 @@ void HipRateLimitCache::finish_oldest(std::deque<Staged>& inflight) {
   autogrow(inflight);
 }
 
-// Peek / Forget: the request's descriptors as one rl_batch of one request, built and handed to
-// rl_peek / rl_forget by the submitter thread (a control call), at the time it reads there.
+// Peek / Forget / Set: the request's descriptors as one rl_batch of one request, built and handed
+// to rl_peek / rl_forget / rl_set by the submitter thread (a control call), at the time it reads
+// there. values != nullptr: a Set, with `keep` (RL_SET_KEEP_*) or-ed into every value's flags.
 std::vector<HipRateLimitCache::PeekStatus> HipRateLimitCache::peek_call(
-    const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits, bool forget) {
+    const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits, bool forget,
+    const std::vector<PeekStatus>* values, uint32_t keep) {
   if (request.Descriptors.size() != limits.size())
     throw std::logic_error("assert: len(request.Descriptors) == len(limits)");
+  if (values && values->size() != limits.size()) throw std::logic_error("assert: len(values) == len(limits)");
   const size_t n = limits.size();
   // GenerateCacheKey prefixes (cache_key.go:57-65), on the caller's thread
   std::vector<uint8_t> blob;
@@ -388,7 +391,20 @@ std::vector<HipRateLimitCache::PeekStatus> HipRateLimitCache::peek_call(
     b.req_of = req_of.data();
     b.now = &now;
     std::vector<rl_peek_reply> rep(n);
-    if (forget ? rl_forget(eng_, &b, rep.data()) : rl_peek(eng_, &b, rep.data())) return rl_last_error(eng_);
+    if (values) {
+      std::vector<rl_peek_reply> val(n);
+      for (size_t i = 0; i < n; ++i) {
+        const PeekStatus& v = (*values)[i];
+        val[i].count = v.Count;
+        val[i].ttl_s = v.TtlSeconds;
+        val[i].cached_s = v.CachedSeconds;
+        val[i].flags = (v.Found ? RL_PEEK_FOUND : 0u) | (v.LocalCached ? RL_PEEK_LOCAL_CACHED : 0u) | keep;
+      }
+      if (rl_set(eng_, &b, val.data(), rep.data())) return rl_last_error(eng_);
+      grow_after_ctl_ = true;  // the call may have claimed slots: the watermark check of a completed batch
+    } else if (forget ? rl_forget(eng_, &b, rep.data()) : rl_peek(eng_, &b, rep.data())) {
+      return rl_last_error(eng_);
+    }
     for (size_t i = 0; i < n; ++i) {
       PeekStatus& s = result[i];
       s.Found = (rep[i].flags & RL_PEEK_FOUND) != 0;
@@ -410,6 +426,15 @@ std::vector<HipRateLimitCache::PeekStatus> HipRateLimitCache::Peek(
 std::vector<HipRateLimitCache::PeekStatus> HipRateLimitCache::Forget(
     const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits) {
   return peek_call(request, limits, true);
+}
+
+std::vector<HipRateLimitCache::PeekStatus> HipRateLimitCache::Set(
+    const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits,
+    const std::vector<PeekStatus>& values, bool keep_counter, bool keep_cache) {
+  // HIP_LOCAL_CACHE=freecache: the device cache is unused, the cache part is ignored
+  const uint32_t keep = (keep_counter ? (uint32_t)RL_SET_KEEP_COUNTER : 0u) |
+                        (keep_cache || fc_ ? (uint32_t)RL_SET_KEEP_CACHE : 0u);
+  return peek_call(request, limits, false, &values, keep);
 }
 
 DoLimitResponse HipRateLimitCache::DoLimit(const RateLimitRequest& request,
@@ -750,6 +775,10 @@ void HipRateLimitCache::submitter() {
       inflight.clear();
       autogrow(inflight);
       const std::string msg = first->ctl();
+      if (grow_after_ctl_) {  // a Set: the auto-grow check, as after a completed batch
+        grow_after_ctl_ = false;
+        autogrow(inflight);
+      }
       if (msg.empty()) first->done.set_value();
       else first->done.set_exception(std::make_exception_ptr(RedisError("hip backend: " + msg)));
       done_calls(1);

@@ -241,6 +241,19 @@ class HipRateLimitCache : public RateLimitCache {
   std::vector<PeekStatus> Forget(const RateLimitRequest& request,
                                  const std::vector<std::shared_ptr<RateLimit>>& limits);
 
+  // Set (rl_hip.h "Set"): Redis SET key n EX ttl per descriptor, and the string's device
+  // local-cache entry: values[i] is what descriptor i's key string holds afterwards (Found: Count
+  // with TtlSeconds, else DEL; LocalCached: CachedSeconds, else no entry), keep_counter /
+  // keep_cache leave that part of every descriptor as it is. Returns what Peek would have
+  // returned just before. A control call exactly like Forget: its place in the serial order, the
+  // time taken on the submitter thread, the trace hook's kTraceControl, registration of new
+  // (RequestsPerUnit, unit) pairs. After it the auto-grow check runs as after a completed batch
+  // (a Set can claim slots). HIP_LOCAL_CACHE=freecache: the cache part is ignored, as the device
+  // cache is unused there. HipRoutedRateLimitCache has no Set yet (rl_hip.h "Set", out of scope).
+  std::vector<PeekStatus> Set(const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits,
+                              const std::vector<PeekStatus>& values, bool keep_counter = false,
+                              bool keep_cache = false);
+
   // Resize (rl_hip.h "Resize"): the counter table moved into one of log2_slots[u] slots per window
   // generation for home unit u (0 keeps that unit's size), on the device, every counter kept. A
   // control call like Save / Load: every DoLimit enqueued before it is decided first, rl_resize
@@ -293,7 +306,9 @@ class HipRateLimitCache : public RateLimitCache {
   void submitter();
   void control(std::function<std::string()> f);
   std::vector<PeekStatus> peek_call(const RateLimitRequest& request,
-                                    const std::vector<std::shared_ptr<RateLimit>>& limits, bool forget);
+                                    const std::vector<std::shared_ptr<RateLimit>>& limits, bool forget,
+                                    const std::vector<PeekStatus>* values = nullptr, uint32_t keep = 0);
+  bool grow_after_ctl_ = false;  // set by a Set's control call, read by the submitter behind it
   uint32_t rule_id(const RateLimitLimit& l, bool shadow);
   bool fits(const Staged& st, const PendingCall& c) const;
   bool compactable(const PendingCall& c) const;

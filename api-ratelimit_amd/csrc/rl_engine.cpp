@@ -23,6 +23,7 @@
 #include "rl_hip.h"
 #include "rl_internal.h"
 #include "rl_resolve.h"
+#include "rl_set.h"
 #include "rl_snapshot.h"
 
 namespace rlhip {
@@ -91,12 +92,14 @@ namespace {
 
 enum KernelId {
   KT_FINGERPRINT, KT_HISTOGRAM, KT_HIST_SCAN, KT_SORT_PASS, KT_SCAN, KT_LEADER, KT_DECIDE, KT_FALLBACK, KT_MEMSET,
-  KT_CAND, KT_V4_HIST, KT_V4_SCAN, KT_V4_PLACE, KT_V4_GROUP, KT_RESOLVE, KT_RULE_STATS, KT_CACHE_STATS, KT_CENSUS, KT_COUNT
+  KT_CAND, KT_V4_HIST, KT_V4_SCAN, KT_V4_PLACE, KT_V4_GROUP, KT_RESOLVE, KT_RULE_STATS, KT_CACHE_STATS, KT_CENSUS,
+  KT_SET_INDEX, KT_SET_PLAN, KT_SET_APPLY, KT_COUNT
 };
 const char* const kKernelNames[KT_COUNT] = {"k_fingerprint", "k_histogram", "k_hist_scan", "k_sort_pass", "k_scan",
                                             "k_leader",      "k_decide",    "fallback",    "memset",      "k_cand_state",
                                             "k4_hist",       "k4_scan",     "k4_place",    "k4_group",
-                                            "k_resolve",     "k_rule_stats", "k_cache_stats", "k_census"};
+                                            "k_resolve",     "k_rule_stats", "k_cache_stats", "k_census",
+                                            "k_set_index",   "k_set_plan",  "k_set_apply"};
 
 enum Mode { MODE_LSD = 1, MODE_LSD_FULL = 2, MODE_V4 = 4 };
 
@@ -159,6 +162,12 @@ struct rl_engine {
   CensusCtl* h_census = nullptr;     // pinned
   uint32_t census_blocks = 1024;     // k_census' grid bound (RL_DIAG_CENSUS_BLOCKS)
   int cstats_ensure();
+  // rl_set's scratch (rl_set.h): the index, the per-descriptor arrays, the staged values and the
+  // control block with its pinned copy, allocated at the first call and kept
+  SetScratch set_sc{};
+  rl_peek_reply* d_set_vals = nullptr;
+  SetCtl* h_set_ctl = nullptr;
+  int set_ensure();
   // what is folded in behind a batch: COUNT_RULE (k_rule_stats) | COUNT_CACHE (k_cache_stats)
   enum : uint32_t { COUNT_RULE = 1u, COUNT_CACHE = 2u };
   int count_batch(const rl_batch& b, const rl_status* out, const EngineCtl* ctl, uint32_t which);
@@ -1281,7 +1290,7 @@ void rl_destroy(rl_engine* e) {
   for (void* p : {(void*)e->v4_hoff, (void*)e->v4_dfr, (void*)e->v4_hb,
                   e->v4_scratch, (void*)e->d_poison, (void*)e->d_tree_nodes,
                   (void*)e->d_tree_slots, (void*)e->d_tree_names, (void*)e->d_tree_fnodes, (void*)e->d_tree_fslots, (void*)e->d_res, (void*)e->d_res_flags, (void*)e->table, (void*)e->d_occ,
-                  (void*)e->d_rules, (void*)e->d_rstats, (void*)e->d_cstats, (void*)e->d_census, (void*)e->keys_orig, (void*)e->keys_a, (void*)e->keys_b, (void*)e->vals_a,
+                  (void*)e->d_rules, (void*)e->d_rstats, (void*)e->d_cstats, (void*)e->d_census, (void*)e->set_sc.index, (void*)e->set_sc.val, (void*)e->set_sc.desc, (void*)e->set_sc.ctl, (void*)e->d_set_vals, (void*)e->keys_orig, (void*)e->keys_a, (void*)e->keys_b, (void*)e->vals_a,
                   (void*)e->vals_b, (void*)e->recs, (void*)e->srec, (void*)e->seg, (void*)e->offs,
                   (void*)e->hist_part, (void*)e->fp_part, (void*)e->fp_part2, (void*)e->tile_heads,
                   (void*)e->zero_block, (void*)e->d_cand, (void*)e->r_tmp, (void*)e->r_own, (void*)e->r_bcnt,
@@ -1290,6 +1299,7 @@ void rl_destroy(rl_engine* e) {
   hipHostFree(e->h_hot_stage);
   hipHostFree(e->h_route);
   hipHostFree(e->h_census);
+  hipHostFree(e->h_set_ctl);
   for (hipStream_t s : {e->front, e->xin, e->xout, e->own_stream})
     if (s) hipStreamDestroy(s);
   delete e;
@@ -2215,12 +2225,8 @@ static int peek_enter(rl_engine* e, const rl_batch* b, const char* what, bool ho
   return 0;
 }
 
-// rl_peek / rl_forget: validate on the host, stage, look up (and clear), copy the replies out.
-static int peek_host(rl_engine* e, const rl_batch* b, rl_peek_reply* out, bool forget) {
-  const char* what = forget ? "rl_forget" : "rl_peek";
-  int rc = peek_enter(e, b, what, true);
-  if (rc) return rc;
-  if (b->n_desc && !forget && !out) return e->fail(RL_EINVAL, "rl_peek: null reply array");
+// What the host forms check of a batch's contents before anything is staged.
+static int peek_check(rl_engine* e, const rl_batch* b, const char* what) {
   for (uint32_t r = 0; r < b->n_req; ++r)
     if (b->now[r] < 0 || b->now[r] > MAX_NOW)
       return e->fail(RL_EINVAL, "%s: request %u: time %lld outside [0, 0xFFFD0000]", what, r, (long long)b->now[r]);
@@ -2233,11 +2239,15 @@ static int peek_host(rl_engine* e, const rl_batch* b, rl_peek_reply* out, bool f
     if (b->rule_id[i] != RL_NIL_RULE && b->rule_id[i] >= e->n_rules)
       return e->fail(RL_EINVAL, "%s: descriptor %u: unknown rule id %u", what, i, b->rule_id[i]);
   }
-  if (!b->n_desc) return 0;
-  // Nothing is in flight, so every host staging slot is idle. The slot after the next submit's is
-  // used: rl_host_acquire may have handed that one out already, and only a slot's pinned outputs
-  // (never touched here) back the views of rl_wait_view. The device outputs of the slot hold the
-  // replies (16 B against the 20 B of a status).
+  return 0;
+}
+
+// Stage a checked, non-empty host batch: d = the batch with device pointers, g = the slot used.
+// Nothing is in flight, so every host staging slot is idle. The slot after the next submit's is
+// used: rl_host_acquire may have handed that one out already, and only a slot's pinned outputs
+// (never touched here) back the views of rl_wait_view. The device outputs of the slot hold the
+// replies (16 B against the 20 B of a status).
+static int peek_stage(rl_engine* e, const rl_batch* b, rl_batch& d, rl_peek_reply*& d_rep) {
   rl_engine::Stage& g = e->stage[(e->sub_seq + 1) % HSLOTS];
   uint8_t* h = g.h_in;
   struct Arr { const void* src; size_t o, n; } arrs[] = {
@@ -2252,7 +2262,7 @@ static int peek_host(rl_engine* e, const rl_batch* b, rl_peek_reply* out, bool f
   for (auto& a : arrs)
     if (he == hipSuccess) he = hipMemcpyAsync(g.d_in + a.o, h + a.o, a.n, hipMemcpyHostToDevice, e->stream);
   if (he != hipSuccess) return e->hip_fail(he, "peek staging");
-  rl_batch d = *b;
+  d = *b;
   d.prefix_blob = g.d_in;
   d.prefix_off = reinterpret_cast<const uint32_t*>(g.d_in + e->o_off);
   d.rule_id = reinterpret_cast<const uint32_t*>(g.d_in + e->o_rule);
@@ -2260,12 +2270,28 @@ static int peek_host(rl_engine* e, const rl_batch* b, rl_peek_reply* out, bool f
   d.now = reinterpret_cast<const int64_t*>(g.d_in + e->o_now);
   d.hits_addend = nullptr;
   d.ttl_jitter = nullptr;
-  rl_peek_reply* d_rep = reinterpret_cast<rl_peek_reply*>(g.d_out);
+  d_rep = reinterpret_cast<rl_peek_reply*>(g.d_out);
   static_assert(sizeof(rl_peek_reply) <= sizeof(rl_status), "the replies fit the slot's status array");
+  return 0;
+}
+
+// rl_peek / rl_forget: validate on the host, stage, look up (and clear), copy the replies out.
+static int peek_host(rl_engine* e, const rl_batch* b, rl_peek_reply* out, bool forget) {
+  const char* what = forget ? "rl_forget" : "rl_peek";
+  int rc = peek_enter(e, b, what, true);
+  if (rc) return rc;
+  if (b->n_desc && !forget && !out) return e->fail(RL_EINVAL, "rl_peek: null reply array");
+  rc = peek_check(e, b, what);
+  if (rc) return rc;
+  if (!b->n_desc) return 0;
+  rl_batch d;
+  rl_peek_reply* d_rep = nullptr;
+  rc = peek_stage(e, b, d, d_rep);
+  if (rc) return rc;
   // the replies first (the state before the call, for every duplicate), then the clears
   if (out) launch_peek(e->stream, d, e->d_rules, e->n_rules, e->cfg.hash_seed, e->tab, d_rep, false);
   if (forget) launch_peek(e->stream, d, e->d_rules, e->n_rules, e->cfg.hash_seed, e->tab, d_rep, true);
-  he = hipGetLastError();
+  hipError_t he = hipGetLastError();
   if (he == hipSuccess && out)
     he = hipMemcpyAsync(out, d_rep, (size_t)b->n_desc * sizeof(rl_peek_reply), hipMemcpyDeviceToHost, e->stream);
   if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
@@ -2281,6 +2307,143 @@ int rl_peek(rl_engine* e, const rl_batch* b, rl_peek_reply* out) {
 int rl_forget(rl_engine* e, const rl_batch* b, rl_peek_reply* out_or_null) {
   if (!e || !b) return RL_EINVAL;
   return peek_host(e, b, out_or_null, true);
+}
+
+// ---- Set ------------------------------------------------------------------------------------
+int rl_engine::set_ensure() {
+  if (set_sc.index) return 0;
+  const uint64_t n = cfg.max_batch_desc ? cfg.max_batch_desc : 1u;
+  uint32_t lg = 6;
+  while ((1ull << lg) < 2 * n) ++lg;
+  SetScratch sc{};
+  rl_peek_reply* vals = nullptr;
+  SetCtl* hc = nullptr;
+  hipError_t he = hipMalloc(&sc.index, sizeof(SetEntry) << lg);
+  if (he == hipSuccess) he = hipMalloc(&sc.val, n * sizeof(SetVal));
+  if (he == hipSuccess) he = hipMalloc(&sc.desc, n * sizeof(SetDesc));
+  if (he == hipSuccess) he = hipMalloc(&sc.ctl, sizeof(SetCtl));
+  if (he == hipSuccess) he = hipMalloc(&vals, n * sizeof(rl_peek_reply));
+  if (he == hipSuccess) he = hipHostMalloc(&hc, sizeof(SetCtl), hipHostMallocDefault);
+  if (he != hipSuccess) {
+    (void)hipGetLastError();
+    for (void* p : {(void*)sc.index, (void*)sc.val, (void*)sc.desc, (void*)sc.ctl, (void*)vals}) hipFree(p);
+    return hip_fail(he, "rl_set scratch allocation");
+  }
+  sc.log2_entries = lg;
+  set_sc = sc;
+  d_set_vals = vals;
+  h_set_ctl = hc;
+  return 0;
+}
+
+// rl_set: every check first (host: shape, values, window generations; device: one identity per
+// index entry, the claims per region against the load limits), then the applying pass, then the
+// occupancy into the mirror and onto the device as rl_resize publishes it.
+int rl_set(rl_engine* e, const rl_batch* b, const rl_peek_reply* values, rl_peek_reply* out) {
+  if (!e || !b) return RL_EINVAL;
+  int rc = peek_enter(e, b, "rl_set", true);
+  if (rc) return rc;
+  if (e->cfg.max_batch_desc > SET_MAX_DESC)
+    return e->fail(RL_ECAPACITY, "rl_set: max_batch_desc %u above 2^29", e->cfg.max_batch_desc);
+  if (b->n_desc && !values) return e->fail(RL_EINVAL, "rl_set: null value array");
+  rc = peek_check(e, b, "rl_set");
+  if (rc) return rc;
+  uint32_t gcall[8] = {};  // the call's window generation per region (0: writes nothing there)
+  for (uint32_t i = 0; i < b->n_desc; ++i) {
+    if (b->rule_id[i] == RL_NIL_RULE) continue;
+    const rl_peek_reply& v = values[i];
+    const bool wc = !(v.flags & RL_SET_KEEP_COUNTER);
+    const bool wf = !(v.flags & RL_SET_KEEP_CACHE) && e->tab.local_cache;
+    if (!wc && !wf) continue;  // a peek
+    const DevRule& R = e->h_rules[b->rule_id[i]];
+    const uint64_t t = (uint64_t)b->now[b->req_of[i]];
+    if (wc && (v.flags & RL_PEEK_FOUND) && !per_second_store(e->tab, R.unit)) {
+      if (!v.ttl_s) return e->fail(RL_EINVAL, "rl_set: descriptor %u: a found main-store value with ttl_s == 0", i);
+      if (t + v.ttl_s >= (1ull << 32))
+        return e->fail(RL_EINVAL, "rl_set: descriptor %u: time + ttl_s is not below 2^32", i);
+    }
+    if (wf && (v.flags & RL_PEEK_LOCAL_CACHED)) {
+      if (!v.cached_s) return e->fail(RL_EINVAL, "rl_set: descriptor %u: a cached value with cached_s == 0", i);
+      if (t + v.cached_s >= (1ull << 32))
+        return e->fail(RL_EINVAL, "rl_set: descriptor %u: time + cached_s is not below 2^32", i);
+    }
+    const Place pl = place_of((uint32_t)(t / R.div) * R.div);
+    if (gcall[pl.region] && gcall[pl.region] != pl.gen)
+      return e->fail(RL_EINVAL, "rl_set: descriptor %u: a second window generation (%u after %u) of table region %u in "
+                                "one call: split the call", i, pl.gen, gcall[pl.region], pl.region);
+    gcall[pl.region] = pl.gen;
+  }
+  for (int r = 0; r < 8; ++r) {
+    const uint32_t G = gcall[r], og = e->occ[r].gen;  // nothing is in flight: the mirror's are the table's
+    if (G && G < og && !(lazy_region(e->tab.lag, (uint32_t)r) && G + 2u == og))
+      return e->fail(RL_EINVAL, "rl_set: window generation %u of table region %d is over (the region's newest is %u)",
+                     G, r, og);
+  }
+  if (!b->n_desc) return 0;
+  rc = e->set_ensure();
+  if (rc) return rc;
+  rl_batch d;
+  rl_peek_reply* d_rep = nullptr;
+  rc = peek_stage(e, b, d, d_rep);
+  if (rc) return rc;
+  SetScratch sc = e->set_sc;
+  sc.log2_entries = 6;
+  while ((1ull << sc.log2_entries) < 2ull * b->n_desc) ++sc.log2_entries;  // <= the allocation's: n_desc <= max_batch_desc
+  const size_t nbytes = (size_t)b->n_desc * sizeof(rl_peek_reply);
+  hipError_t he = hipMemcpyAsync(e->d_set_vals, values, nbytes, hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipMemsetAsync(sc.index, 0, sizeof(SetEntry) << sc.log2_entries, e->stream);
+  if (he == hipSuccess) he = hipMemsetAsync(sc.ctl, 0, sizeof(SetCtl), e->stream);
+  if (he == hipSuccess) {
+    // the replies first: the state before the call, for every duplicate
+    if (out) launch_peek(e->stream, d, e->d_rules, e->n_rules, e->cfg.hash_seed, e->tab, d_rep, false);
+    e->timed(KT_SET_INDEX, [&] {
+      launch_set_index(e->stream, d, e->d_rules, e->n_rules, e->cfg.hash_seed, e->tab, e->d_set_vals, sc);
+    });
+    e->timed(KT_SET_PLAN, [&] { launch_set_plan(e->stream, b->n_desc, e->tab, sc); });
+    he = hipGetLastError();
+  }
+  if (he == hipSuccess) he = hipMemcpyAsync(e->h_set_ctl, sc.ctl, sizeof(SetCtl), hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  if (he != hipSuccess) return e->hip_fail(he, "rl_set (nothing written)");
+  if (e->timing) e->fold_marks();
+  const SetCtl* hc = e->h_set_ctl;
+  if (hc->err & SET_ERR_MIXED)
+    return e->fail(RL_EDEVICE, "rl_set: two key strings of the call share one 64-bit sort key: split the call "
+                               "(nothing written)");
+  if (hc->err) return e->fail(RL_EDEVICE, "rl_set: the call's index overflowed (nothing written)");
+  for (int r = 0; r < 8; ++r) {
+    const uint32_t c = hc->plan[r][0];
+    if (!c) continue;
+    const uint64_t live = region_live(e->occ[r], lazy_region(e->tab.lag, (uint32_t)r), gcall[r]);
+    if (live + c > e->occ[r].limit)
+      return e->fail(RL_ENOSPC, "rl_set: table region %d holds %llu live slots and the call claims %u, over its load "
+                                "limit of %u (nothing written)", r, (unsigned long long)live, c, e->occ[r].limit);
+  }
+  e->timed(KT_SET_APPLY, [&] { launch_set_apply(e->stream, b->n_desc, e->tab, sc); });
+  he = hipGetLastError();
+  if (he == hipSuccess) he = hipMemcpyAsync(e->h_set_ctl, sc.ctl, sizeof(SetCtl), hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess && out) he = hipMemcpyAsync(out, d_rep, nbytes, hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  if (he != hipSuccess) return e->hip_fail(he, "rl_set: applying pass (the table may hold part of the call)");
+  if (e->timing) e->fold_marks();
+  if (hc->err)
+    return e->fail(RL_EDEVICE, "rl_set: a region had no free slot left (the table may hold part of the call)");
+  RegionOcc nocc[8];
+  uint64_t claims = 0;
+  for (int r = 0; r < 8; ++r) {
+    nocc[r] = e->occ[r];
+    const uint32_t c = hc->claim[r][0];
+    if (c) occ_advance(nocc[r], lazy_region(e->tab.lag, (uint32_t)r), gcall[r], c);
+    claims += c;
+  }
+  if (claims) {
+    he = hipMemcpy(e->d_occ, nocc, sizeof nocc, hipMemcpyHostToDevice);
+    if (he != hipSuccess) return e->hip_fail(he, "rl_set: publish occupancy");
+    memcpy(e->occ, nocc, sizeof nocc);
+    e->st.inserted_keys += claims;
+    e->st.live_keys = e->live_total();
+  }
+  return 0;
 }
 
 int rl_peek_device(rl_engine* e, const rl_batch* b, rl_peek_reply* d_out) {

@@ -1,5 +1,6 @@
 // rl_peek.h — the lookup both peek kernels end in (rl_peek.hip k_peek: from a descriptor;
-// rl_peek_routed.hip k_peek_routed: from a routed record), one function so the two cannot drift.
+// rl_peek_routed.hip k_peek_routed: from a routed record), one function so the two cannot drift,
+// and the key identity it starts from, which rl_set.hip shares.
 #pragma once
 #include "rl_decide.h"
 
@@ -7,6 +8,29 @@ namespace rlhip {
 namespace peek {
 
 constexpr int NT = 256;
+
+// A key string's identity from its prefix state, its request time and its rule: the window start,
+// the table place (region, window generation), the sort key and the fingerprint's low lane (the
+// slot's tag). One function for every by-key entry point (peek, forget, rl_set.hip's set).
+struct KeyIdent {
+  uint32_t ws;
+  Place pl;
+  uint64_t key, lo;
+};
+__device__ __forceinline__ KeyIdent key_ident(const FpState& s, const uint32_t n32, const DevRule& rr) {
+  // now / divider by 32-bit multiply-high (rl_tile.h key_of: exact for every 32-bit now)
+  const uint32_t q60 = __umulhi(n32, 0x88888889u) >> 5, q3600 = __umulhi(n32, 0x91A2B3C5u) >> 11,
+                 q86400 = __umulhi(n32 >> 7, 0xC22E4507u) >> 9;
+  const uint32_t unit = rr.unit;
+  const uint32_t widx = unit == RL_UNIT_SECOND ? n32 : unit == RL_UNIT_MINUTE ? q60 : unit == RL_UNIT_HOUR ? q3600 : q86400;
+  KeyIdent k;
+  k.ws = widx * rr.div;  // (now/divider)*divider  cache_key.go:66-68
+  uint64_t hi;
+  fp_final(s, (uint64_t)k.ws, hi, k.lo);
+  k.pl = place_of(k.ws);
+  k.key = make_sort_key(k.pl.region, hi);
+  return k;
+}
 
 // From a key's prefix state, its request time (in [0, MAX_NOW], checked by the caller) and its
 // rule: the window start, the key string's identity and table place, the lookup (issued first:
@@ -17,16 +41,10 @@ constexpr int NT = 256;
 template <bool FORGET>
 __device__ __forceinline__ rl_peek_reply peek_key(const FpState& s, const uint32_t n32, const DevRule& rr,
                                                   const TableDesc& tab, rl_peek_reply rep) {
-  // now / divider by 32-bit multiply-high (rl_tile.h key_of: exact for every 32-bit now)
-  const uint32_t q60 = __umulhi(n32, 0x88888889u) >> 5, q3600 = __umulhi(n32, 0x91A2B3C5u) >> 11,
-                 q86400 = __umulhi(n32 >> 7, 0xC22E4507u) >> 9;
+  const KeyIdent id = key_ident(s, n32, rr);
   const uint32_t unit = rr.unit;
-  const uint32_t widx = unit == RL_UNIT_SECOND ? n32 : unit == RL_UNIT_MINUTE ? q60 : unit == RL_UNIT_HOUR ? q3600 : q86400;
-  const uint32_t ws = widx * rr.div;  // (now/divider)*divider  cache_key.go:66-68
-  uint64_t hi, lo;
-  fp_final(s, (uint64_t)ws, hi, lo);
-  const Place pl = place_of(ws);
-  const uint64_t key = make_sort_key(pl.region, hi);
+  const Place pl = id.pl;
+  const uint64_t key = id.key, lo = id.lo;
   const SlotView pre = load_slot(slot_first(tab, key));
   Slot* slot = nullptr;
   KeyState st{0, 0, 0, 0};

@@ -118,6 +118,7 @@ RAW_DTYPE = np.dtype([("after", "<u4"), ("flags", "<u4")])
 # ---- peek / forget (rl_hip.h "Peek / forget") ----
 PEEK_FOUND, PEEK_LOCAL_CACHED, PEEK_NIL, PEEK_PER_SECOND, PEEK_BAD = 1, 2, 4, 8, 16  # rl_peek_reply.flags
 PEEK_DTYPE = np.dtype([("count", "<u4"), ("ttl_s", "<u4"), ("cached_s", "<u4"), ("flags", "<u4")])
+SET_KEEP_COUNTER, SET_KEEP_CACHE = 32, 64  # RL_SET_KEEP_*: rl_set's input-only bits of rl_peek_reply.flags
 PEEK_ROUTED_FORGET = 1  # RL_PEEK_ROUTED_FORGET: rl_peek_routed clears after it has looked every record up
 
 
@@ -293,6 +294,7 @@ ABI = [
     ("rl_peek", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
     ("rl_peek_device", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
     ("rl_forget", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
+    ("rl_set", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_void_p], C.c_int),
     ("rl_peek_routed", [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32], C.c_int),
     ("rl_route_unpack_peek", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     ("rl_router_peek", [C.c_void_p, C.POINTER(RlBatch), C.POINTER(C.c_void_p)], C.c_int),
@@ -774,6 +776,20 @@ class Engine:
         out = np.zeros(b.n_desc, PEEK_DTYPE)
         s = _batch_struct(b)
         self._check(self.lib.rl_forget(self.h, C.byref(s), _ptr(out) or None), "rl_forget")
+        return out
+
+    def set(self, b: Batch, values: np.ndarray, want_out: bool = True):
+        """rl_set of a host batch (hits and jitter ignored): values[i] (PEEK_DTYPE, a peek reply fed
+        back or built by hand, SET_KEEP_* bits allowed) is what descriptor i's key string holds
+        afterwards. Returns the replies as read before the call (PEEK_DTYPE), or None."""
+        values = np.ascontiguousarray(values, PEEK_DTYPE)
+        if values.shape != (b.n_desc,):
+            raise ValueError(f"rl_set: {values.shape[0] if values.ndim == 1 else values.shape} values for "
+                             f"{b.n_desc} descriptors")
+        out = np.zeros(b.n_desc, PEEK_DTYPE) if want_out else None
+        s = _batch_struct(b)
+        self._check(self.lib.rl_set(self.h, C.byref(s), _ptr(values) or None,
+                                    (_ptr(out) or None) if want_out else None), "rl_set")
         return out
 
     def peek_device(self, n_desc: int, n_req: int, blob_bytes: int, ptrs, out_ptr: int):
@@ -1317,6 +1333,22 @@ class HipRateLimitCache:
     def resize(self, log2_slots):
         """Resize the counter table on the device (Engine.resize); 0 keeps a unit's size."""
         return self.engine.resize(log2_slots)
+
+    def set(self, request: RateLimitRequest, limits: list, values, keep_counter: bool = False,
+            keep_cache: bool = False) -> np.ndarray:
+        """HipRateLimitCache::Set (rl_cache.hpp): values[i] (PEEK_DTYPE: count, ttl_s, cached_s and
+        the PEEK_FOUND / PEEK_LOCAL_CACHED flags) is what descriptor i's key string holds afterwards,
+        at the time source's now; keep_counter / keep_cache leave that part of every descriptor as
+        it is. Returns the replies as read before the call. Spends nothing: no hit, no stat."""
+        assert len(request.Descriptors) == len(limits), "assert: len(request.Descriptors) == len(limits)"
+        rules = [NIL_RULE if lim is None else self._rule(lim.Limit, lim.ShadowMode) for lim in limits]
+        if self.dirty:
+            self.engine.load_rules(self.rules)
+            self.dirty = False
+        v = np.array(values, PEEK_DTYPE).reshape(len(limits)).copy()
+        v["flags"] |= (SET_KEEP_COUNTER if keep_counter else 0) | (SET_KEEP_CACHE if keep_cache else 0)
+        b = build_batch([(request.Domain, request.Descriptors, rules, request.HitsAddend, self.time_source())])
+        return self.engine.set(b, v)
 
     def do_limit_batch(self, calls) -> list:
         reqs = []

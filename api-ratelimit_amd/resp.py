@@ -15,6 +15,11 @@ tests replay into `RespStore`, a minimal in-process RESP executor with Redis' IN
 semantics (missing key = 0, post-increment reply); the live path (`replay_to_redis`) runs only
 when `RL_REDIS_ADDR` names a server. Expiry is not simulated: keys carry their window start
 (`src/limiter/cache_key.go:57-68`), so a window never reuses an earlier window's key.
+
+The other direction is the cutover from a live Redis (rl_hip.h "Set"):
+`import_batch` turns what `SCAN` + `GET` + `TTL` return into the batch and values of one
+`Engine.set`, `read_redis` asks a server for them, and a `RespStore` given a clock keeps absolute
+deadlines and lists the same entries with `dump(now)`, which is how the tests cover the path.
 """
 from __future__ import annotations
 
@@ -128,16 +133,34 @@ def _parse_commands(data: bytes):
 
 class RespStore:
     """A minimal RESP executor for INCRBY/EXPIRE with Redis' semantics: INCRBY on a missing
-    key starts from 0 and replies the post-value; EXPIRE replies 1 if the key exists."""
+    key starts from 0 and replies the post-value; EXPIRE replies 1 if the key exists.
 
-    def __init__(self):
+    Without a clock (the default) expiry is not simulated and `ttl` holds the last EXPIRE argument.
+    With one (`clock`, a callable returning unix seconds, or `now=` per execute call) the store
+    records absolute deadlines: a key is gone from its deadline on, as in Redis, and `dump(now)`
+    lists what SCAN + GET + TTL would return."""
+
+    def __init__(self, clock: Optional[Callable[[], int]] = None):
         self.counters: Dict[bytes, int] = {}
         self.ttl: Dict[bytes, int] = {}
+        self.deadline: Dict[bytes, int] = {}
+        self.clock = clock
 
-    def execute(self, data: bytes) -> bytes:
+    def _expire_due(self, key: bytes, now: int):
+        d = self.deadline.get(key)
+        if d is not None and now >= d:
+            self.counters.pop(key, None)
+            self.ttl.pop(key, None)
+            del self.deadline[key]
+
+    def execute(self, data: bytes, now: Optional[int] = None) -> bytes:
+        if now is None and self.clock is not None:
+            now = int(self.clock())
         out = bytearray()
         for parts in _parse_commands(data):
             cmd = parts[0].upper()
+            if now is not None and len(parts) > 1:
+                self._expire_due(parts[1], now)
             if cmd == b"INCRBY":
                 v = self.counters.get(parts[1], 0) + int(parts[2])
                 self.counters[parts[1]] = v
@@ -146,10 +169,24 @@ class RespStore:
                 ok = parts[1] in self.counters
                 if ok:
                     self.ttl[parts[1]] = int(parts[2])
+                    if now is not None:
+                        self.deadline[parts[1]] = now + int(parts[2])
                 out += b":1\r\n" if ok else b":0\r\n"
             else:
                 out += b"-ERR unknown command '" + parts[0] + b"'\r\n"
         return bytes(out)
+
+    def dump(self, now: int) -> List[Tuple[bytes, int, int]]:
+        """[(key, value, ttl_remaining)] of every key alive at `now`, the entry format of
+        import_batch; a key without a deadline reports Redis' TTL reply -1."""
+        out = []
+        for k, v in self.counters.items():
+            d = self.deadline.get(k)
+            if d is None:
+                out.append((k, v, -1))
+            elif now < d:
+                out.append((k, v, d - now))
+        return out
 
 
 def replay_to_redis(data: bytes, host: str, port: int, n_replies: int, timeout: float = 10.0) -> bytes:
@@ -205,3 +242,92 @@ def replay_local(store: RespStore, ps_store: Optional[RespStore], batch: hiprl.B
     incr = incr_replies(cmds, r_main, r_ps)
     check_replies(batch, rules, status, cmds, incr)
     return incr
+
+
+# ---------------------------------------------------------------------------
+# Import from Redis (rl_hip.h "Set", INTEGRATION.md §4f): SCAN + GET + TTL -> Engine.set
+# ---------------------------------------------------------------------------
+def import_batch(entries, now: int, unit_rule: Dict[int, int], per_second: bool = False):
+    """[(key string, value, ttl_remaining)] of one Redis instance, read at `now` -> (Batch, values,
+    skipped) for hiprl.Engine.set: one descriptor per live key, all in one request at `now`.
+
+    A key string is prefix || decimal(window start) and the prefix ends in its last '_'
+    (cache_key.go:57-68), so it splits uniquely. Its unit is the smallest loaded unit u whose
+    current window starts at that second, (now / div(u)) * div(u) == window start; unit_rule[u] is
+    the id of any loaded rule of unit u (a rule's limit plays no part in a key's identity). With
+    per_second=True the list is the REDIS_PERSECOND instance's: only SECOND keys live there. A key
+    whose window is no current window, whose TTL is not positive (-1: no expiry, -2: gone) or whose
+    string does not split goes to `skipped` as (key, reason). Values are taken mod 2^32, the uint32
+    the reference decodes an INCRBY reply into (fixed_cache_impl.go:51). The local over-limit cache
+    is not in Redis: every value leaves it empty, as a restart of the reference service does."""
+    now = int(now)
+    units = [u for u in sorted(unit_rule, key=lambda u: hiprl.UNIT_DIVIDER[u]) if not per_second or u == hiprl.SECOND]
+    blob = bytearray()
+    off, rule, vals, skipped = [0], [], [], []
+    for key, value, ttl in entries:
+        key = key.encode() if isinstance(key, str) else bytes(key)
+        cut = key.rfind(b"_") + 1
+        digits = key[cut:]
+        if cut == 0 or not digits.isdigit() or (len(digits) > 1 and digits[:1] == b"0"):
+            skipped.append((key, "not prefix_<decimal window start>"))
+            continue
+        if int(ttl) <= 0:
+            skipped.append((key, "no positive TTL"))
+            continue
+        ws = int(digits)
+        unit = next((u for u in units if (now // hiprl.UNIT_DIVIDER[u]) * hiprl.UNIT_DIVIDER[u] == ws), None)
+        if unit is None:
+            skipped.append((key, "window is not current"))
+            continue
+        blob += key[:cut]
+        off.append(len(blob))
+        rule.append(unit_rule[unit])
+        vals.append((int(value) & 0xFFFFFFFF, int(ttl), 0, hiprl.PEEK_FOUND))
+    n = len(rule)
+    b = hiprl.Batch(np.frombuffer(bytes(blob), np.uint8).copy(), np.array(off, np.uint32), np.array(rule, np.uint32),
+                    np.zeros(n, np.uint32), np.array([now], np.int64), np.ones(1, np.uint32))
+    return b, np.array(vals, hiprl.PEEK_DTYPE).reshape(n), skipped
+
+
+def _read_reply(f):
+    line = f.readline()
+    if not line.endswith(CRLF):
+        raise hiprl.RedisError("connection closed by redis-server")
+    t, body = line[:1], line[1:-2]
+    if t == b":":
+        return int(body)
+    if t == b"+":
+        return body
+    if t == b"-":
+        raise hiprl.RedisError(body.decode(errors="replace"))
+    if t == b"$":
+        n = int(body)
+        return None if n < 0 else f.read(n + 2)[:-2]
+    if t == b"*":
+        return [_read_reply(f) for _ in range(int(body))]
+    raise hiprl.RedisError(f"unexpected RESP reply type {t!r}")
+
+
+def read_redis(host: str, port: int, timeout: float = 10.0, count: int = 1000):
+    """SCAN every key of a live redis-server, with GET and TTL per key -> ([(key, value, ttl)], now
+    from the server's TIME), the input of import_batch. Unverified: no redis-server exists where
+    this project is built and tested (the tests cover the same path through RespStore.dump);
+    INTEGRATION.md §7 describes the setting it is meant for."""
+    out = []
+    with socket.create_connection((host, port), timeout=timeout) as s, s.makefile("rb") as f:
+        def call(*parts):
+            s.sendall(flat_cmd(*parts))
+            return _read_reply(f)
+        s.sendall(b"*1\r\n$4\r\nTIME\r\n")  # (flat_cmd always sends a key)
+        now = int(_read_reply(f)[0])
+        cursor = b"0"
+        while True:
+            cursor, keys = call("SCAN", cursor, "COUNT", count)
+            for k in keys:
+                v = call("GET", k)
+                t = call("TTL", k)
+                if v is not None and v.lstrip(b"-").isdigit():
+                    out.append((k, int(v), int(t)))
+            if cursor == b"0":
+                break
+    return out, now

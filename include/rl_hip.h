@@ -718,6 +718,72 @@ int rl_peek(rl_engine* e, const rl_batch* host_batch, rl_peek_reply* out);
 int rl_peek_device(rl_engine* e, const rl_batch* device_batch, rl_peek_reply* d_out);
 int rl_forget(rl_engine* e, const rl_batch* host_batch, rl_peek_reply* out_or_null);
 
+/* ---- Set: write counters by key -------------------------------------------
+ * Redis SET key n EX ttl, per store, plus freecache's Set / Del on the string's local over-limit
+ * cache entry: the write that completes rl_peek (read) and rl_forget (clear). It is what a cutover
+ * from a live Redis deployment (resp.py import_batch), a correction of one key and a move of keys
+ * between engines ("peek there, set here") are made of. host_batch is an ordinary batch, read as
+ * rl_peek reads it (hits_addend and ttl_jitter ignored, may be NULL); values[i] says what
+ * descriptor i's key string holds afterwards, in the rl_peek_reply that peek and forget speak;
+ * out (may be NULL) receives what rl_peek would have answered just before the call, duplicates
+ * within the call included (rl_forget's rule). Host memory, synchronous.
+ *
+ * Descriptor i, with t = now[req_of[i]] and its rule's unit giving the store and the window
+ * (RL_NIL_RULE: nothing):
+ *   counter part, unless RL_SET_KEEP_COUNTER:
+ *     RL_PEEK_FOUND      main store: count = values[i].count, expiry = t + ttl_s;
+ *                        per-second store: counter = count (ttl_s ignored: the table keeps no TTL
+ *                        there; count == 0 is the store's "absent", so it reads back as not found
+ *                        and, like a DEL, claims nothing)
+ *     otherwise          DEL on that store, exactly what rl_forget writes
+ *   cache part, unless RL_SET_KEEP_CACHE, and only when rl_config.local_cache is on (else ignored):
+ *     RL_PEEK_LOCAL_CACHED  deadline = t + cached_s;  otherwise  no entry (deadline 0)
+ * RL_PEEK_NIL, RL_PEEK_PER_SECOND and RL_PEEK_BAD in values are ignored, so a peek reply can be fed
+ * back verbatim, and after rl_set(b, v) without KEEP bits rl_peek(b) returns v wherever v's
+ * (count, ttl_s, cached_s) are 0 under a clear flag (PER_SECOND / NIL recomputed; the per-second
+ * count == 0 case above excepted). Each part is written as its own 32-bit stores: two descriptors
+ * that write the two stores of one shared string lose nothing. A descriptor with both KEEP bits
+ * (or KEEP_COUNTER with the local cache off) is a peek.
+ *
+ * Claims: an absent string gets a table slot (zero state first; the pipelines' own claim) only if
+ * the call leaves something in it, a FOUND counter or a cache deadline. A pure DEL or a peek of an
+ * absent string claims nothing.
+ * Duplicates: the same (string, store) may occur several times. The last in descriptor order wins
+ * its counter part, and the last descriptor of the string that writes the cache part wins that
+ * part — a pipeline of Redis SETs. The result does not depend on scheduling.
+ * Occupancy: per region the call claims in, the claims (distinct absent strings that get
+ * something, counted on the device) and the call's window generation there go through the batch's
+ * occupancy update, on the device and in the host mirror: rl_engine_stats.inserted_keys grows by
+ * the claims, live_keys follows, and a region whose generation the call advances leaves its
+ * older slots stale, exactly as a batch does. A region where the call claims nothing keeps its
+ * occupancy word for word. The hot set and the candidate stash hold prefixes and are untouched.
+ *
+ * Refused before anything changes (table, occupancy, mirror, stats and out exactly as before):
+ *   RL_ESTATE     a batch in flight, or between rl_restore_begin and rl_restore_end (an open
+ *                 snapshot does not block the call)
+ *   RL_ECAPACITY  rl_peek's capacity limits (and max_batch_desc above 2^29)
+ *   RL_EINVAL     anything rl_peek refuses; values == NULL with n_desc > 0; of the parts a
+ *                 descriptor writes: a FOUND main-store value with ttl_s == 0, a LOCAL_CACHED value
+ *                 with cached_s == 0, t + ttl_s or t + cached_s not below 2^32; among the
+ *                 descriptors that write something: two window generations of one region in one
+ *                 call (split the call: the batch rule behind a window span error), or a window
+ *                 generation that is neither the region's newest, nor newer, nor a lag region's
+ *                 newest - 2 (that window is over)
+ *   RL_ENOSPC     a region's live slots plus the call's claims there would pass its load limit
+ *   RL_EDEVICE    two identities of the call share one 64-bit sort key (split the call), found by
+ *                 the planning pass: nothing written
+ * Every check above runs before the applying pass, and so does every HIP failure of the staging,
+ * indexing and planning passes (RL_EHIP): nothing written. A failure of the applying pass itself
+ * (RL_EHIP, or RL_EDEVICE for a region without a free slot, which the RL_ENOSPC check rules
+ * out) leaves the table with some of the call's writes and the occupancy not advanced: the engine
+ * is to be reset or restored, as after any failed stream.
+ * The index (32 B x the power of two >= 2 x max_batch_desc) and two per-descriptor scratch arrays
+ * (40 B x max_batch_desc) are allocated at the first call and kept.
+ * Out of scope: a routed rl_router_set (the routed forget's pack and exchanges would carry it;
+ * until then a rank can rl_set the keys it owns), a device-memory public form, a compact wire form. */
+enum { RL_SET_KEEP_COUNTER = 32u, RL_SET_KEEP_CACHE = 64u }; /* rl_peek_reply.flags, input only */
+int rl_set(rl_engine* e, const rl_batch* host_batch, const rl_peek_reply* values, rl_peek_reply* out_or_null);
+
 /* ---- Routed peek / forget --------------------------------------------------
  * The same lookups where the keys are spread over the shards of a router.
  *
