@@ -60,10 +60,11 @@ struct PendingCall {
   // A control call (Save / Load) instead of a request: it keeps its place in the queue, and the
   // submitter runs it with nothing in flight. Returns an error message, empty on success.
   std::function<std::string()> ctl;
-  // HipRoutedRateLimitCache: a Peek (1) or Forget (2) instead of a request, answered at a rule /
-  // stop agreement into `peek`
+  // HipRoutedRateLimitCache: a Peek (1), Forget (2) or Set (3) instead of a request, answered at a
+  // rule / stop agreement into `peek`; a Set's values (with its KEEP bits or-ed in) in `set_vals`
   int kind = 0;
   std::vector<PeekStatus> peek;
+  std::vector<rl_peek_reply> set_vals;
 };
 
 namespace {
@@ -849,10 +850,10 @@ struct HipRoutedRateLimitCache::Step {
 
 namespace {
 // One rank's words in a rule / stop agreement (rl_router_allgather_host, RL_ROUTER_AG_MAX bytes).
-constexpr uint32_t SYNC_RULES = (RL_ROUTER_AG_MAX - 16) / sizeof(rl_rule);
+constexpr uint32_t SYNC_RULES = (RL_ROUTER_AG_MAX - 24) / sizeof(rl_rule);
 struct SyncWords {
   uint32_t stop, n;
-  uint32_t n_peek, n_forget;  // pending Peek / Forget calls of this rank
+  uint32_t n_peek, n_forget, n_set, pad;  // pending Peek / Forget / Set calls of this rank
   rl_rule rules[SYNC_RULES];
 };
 static_assert(sizeof(SyncWords) <= RL_ROUTER_AG_MAX, "sync words");
@@ -964,24 +965,25 @@ bool HipRoutedRateLimitCache::known(const PendingCall& c) {
 // every rank's table in rank order (the first occurrence keeps its id), loaded into the engine.
 // Returns true when every rank asked to stop.
 // Then the control calls: if any rank has pending Peeks every rank makes one rl_router_peek, then
-// the same for Forgets.
+// the same for Forgets, then for Sets (rl_router_set).
 bool HipRoutedRateLimitCache::sync(bool want_stop, std::deque<std::shared_ptr<PendingCall>>& ctl, uint64_t seq) {
   SyncWords mine;
   memset(&mine, 0, sizeof mine);
   mine.stop = want_stop ? 1u : 0u;
-  for (const auto& c : ctl) (c->kind == 1 ? mine.n_peek : mine.n_forget) += 1;
+  for (const auto& c : ctl) (c->kind == 1 ? mine.n_peek : c->kind == 2 ? mine.n_forget : mine.n_set) += 1;
   mine.n = (uint32_t)std::min<size_t>(pending_.size(), SYNC_RULES);
   std::copy(pending_.begin(), pending_.begin() + mine.n, mine.rules);
   std::vector<SyncWords> all(r_.n_shards);
   int rc = rl_router_allgather_host(rt_, &mine, sizeof mine, all.data());
   if (rc) throw RedisError(std::string("rule agreement: ") + rl_router_last_error(rt_));
   n_syncs_ += 1;
-  bool all_stop = true, any_peek = false, any_forget = false;
+  bool all_stop = true, any_peek = false, any_forget = false, any_set = false;
   const size_t before = rules_.size();
   for (const SyncWords& w : all) {
     all_stop &= w.stop != 0;
     any_peek |= w.n_peek != 0;
     any_forget |= w.n_forget != 0;
+    any_set |= w.n_set != 0;
     for (uint32_t i = 0; i < w.n; ++i) {
       const auto k = std::make_pair(w.rules[i].requests_per_unit, w.rules[i].unit);
       if (ids_.emplace(k, (uint32_t)rules_.size()).second) rules_.push_back(w.rules[i]);
@@ -997,10 +999,11 @@ bool HipRoutedRateLimitCache::sync(bool want_stop, std::deque<std::shared_ptr<Pe
   }
   if (any_peek) run_control(1, ctl, seq);
   if (any_forget) run_control(2, ctl, seq);
+  if (any_set) run_control(3, ctl, seq);
   return all_stop;
 }
 
-// One collective rl_router_peek (kind 1) / rl_router_forget (kind 2) at an agreement: this rank's
+// One collective rl_router_peek (kind 1) / rl_router_forget (kind 2) / rl_router_set (kind 3) at an agreement: this rank's
 // pending calls of the kind whose limits are agreed, in enqueue order, as one request each, as far
 // as one router batch holds them (the others wait for the following agreement); an empty batch
 // when there are none.
@@ -1009,6 +1012,7 @@ void HipRoutedRateLimitCache::run_control(int kind, std::deque<std::shared_ptr<P
   std::vector<uint8_t> blob;
   std::vector<uint32_t> off(1, 0u), rule, req_of;
   std::vector<int64_t> now;
+  std::vector<rl_peek_reply> val;  // (a Set's)
   const size_t max_blob = (size_t)s_.batch_limit * 128u;
   for (auto it = ctl.begin(); it != ctl.end();) {
     PendingCall& c = **it;
@@ -1029,6 +1033,7 @@ void HipRoutedRateLimitCache::run_control(int kind, std::deque<std::shared_ptr<P
       rule.push_back(lim ? ids_.at(limit_key(*lim)) : RL_NIL_RULE);
       req_of.push_back(rq);
     }
+    val.insert(val.end(), c.set_vals.begin(), c.set_vals.end());
     calls.push_back(*it);
     it = ctl.erase(it);
   }
@@ -1044,7 +1049,11 @@ void HipRoutedRateLimitCache::run_control(int kind, std::deque<std::shared_ptr<P
   b.now = now.data();
   std::vector<rl_peek_reply> rep(std::max<size_t>(1, rule.size()));
   rl_peek_reply* outs[1] = {rep.data()};
-  const int rc = kind == 1 ? rl_router_peek(rt_, &b, outs) : rl_router_forget(rt_, &b, outs);
+  val.resize(std::max<size_t>(1, val.size()));
+  const rl_peek_reply* vals[1] = {val.data()};
+  const int rc = kind == 1   ? rl_router_peek(rt_, &b, outs)
+                 : kind == 2 ? rl_router_forget(rt_, &b, outs)
+                             : rl_router_set(rt_, &b, vals, outs);
   if (rc) {
     const std::string msg = rl_router_last_error(rt_);
     fail(calls, msg);
@@ -1068,14 +1077,25 @@ void HipRoutedRateLimitCache::run_control(int kind, std::deque<std::shared_ptr<P
   done_calls(calls.size());
 }
 
-// Peek / Forget: the caller's side. GenerateCacheKey prefixes as DoLimit builds them (no hit, no
+// Peek / Forget / Set: the caller's side. GenerateCacheKey prefixes as DoLimit builds them (no hit, no
 // stat), queued behind the calls enqueued before; the submitter keeps it for the next agreement.
 std::vector<PeekStatus> HipRoutedRateLimitCache::peek_call(const RateLimitRequest& request,
                                                            const std::vector<std::shared_ptr<RateLimit>>& limits,
-                                                           int kind) {
+                                                           int kind, const std::vector<PeekStatus>* values,
+                                                           uint32_t keep) {
   if (request.Descriptors.size() != limits.size())
     throw std::logic_error("assert: len(request.Descriptors) == len(limits)");
+  if (values && values->size() != limits.size()) throw std::logic_error("assert: len(values) == len(limits)");
   auto call = std::make_shared<PendingCall>();
+  if (values) {
+    call->set_vals.resize(values->size());
+    for (size_t i = 0; i < values->size(); ++i) {
+      const PeekStatus& v = (*values)[i];
+      call->set_vals[i] = rl_peek_reply{v.Count, v.TtlSeconds, v.CachedSeconds,
+                                        (v.Found ? (uint32_t)RL_PEEK_FOUND : 0u) |
+                                            (v.LocalCached ? (uint32_t)RL_PEEK_LOCAL_CACHED : 0u) | keep};
+    }
+  }
   call->req = &request;
   call->limits = &limits;
   call->kind = kind;
@@ -1115,6 +1135,15 @@ std::vector<PeekStatus> HipRoutedRateLimitCache::Peek(const RateLimitRequest& re
 std::vector<PeekStatus> HipRoutedRateLimitCache::Forget(const RateLimitRequest& request,
                                                         const std::vector<std::shared_ptr<RateLimit>>& limits) {
   return peek_call(request, limits, 2);
+}
+
+std::vector<PeekStatus> HipRoutedRateLimitCache::Set(const RateLimitRequest& request,
+                                                     const std::vector<std::shared_ptr<RateLimit>>& limits,
+                                                     const std::vector<PeekStatus>& values, bool keep_counter,
+                                                     bool keep_cache) {
+  const uint32_t keep = (keep_counter ? (uint32_t)RL_SET_KEEP_COUNTER : 0u) |
+                        (keep_cache ? (uint32_t)RL_SET_KEEP_CACHE : 0u);
+  return peek_call(request, limits, 3, &values, keep);
 }
 
 // The rank's step loop: rule / stop agreement every rule_sync_every steps (nothing in flight),

@@ -401,6 +401,15 @@ class HipRoutedRateLimitCache : public RateLimitCache {
   std::vector<PeekStatus> Peek(const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits);
   std::vector<PeekStatus> Forget(const RateLimitRequest& request,
                                  const std::vector<std::shared_ptr<RateLimit>>& limits);
+  // Set (rl_hip.h "Routed set"): HipRateLimitCache::Set's signature and PeekStatus, written at the
+  // owner of each key through rl_router_set, all owners or none. A third control kind beside Peek
+  // and Forget: agreed at the rule / stop agreement (every rank's words carry its number of pending
+  // Sets), run after the agreement's Peeks and Forgets, every rank's pending Sets as one
+  // rl_router_set (a rank with none passes an empty batch), reported to the trace hook as (the next
+  // step's sequence number, kTraceControl). Returns what Peek would have returned just before.
+  std::vector<PeekStatus> Set(const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits,
+                              const std::vector<PeekStatus>& values, bool keep_counter = false,
+                              bool keep_cache = false);
 
   struct RoutedStats {
     uint64_t steps, empty_steps, rule_syncs, rules, held_calls;
@@ -418,7 +427,8 @@ class HipRoutedRateLimitCache : public RateLimitCache {
   bool sync(bool want_stop, std::deque<std::shared_ptr<PendingCall>>& ctl, uint64_t seq);
   void run_control(int kind, std::deque<std::shared_ptr<PendingCall>>& ctl, uint64_t seq);
   std::vector<PeekStatus> peek_call(const RateLimitRequest& request,
-                                    const std::vector<std::shared_ptr<RateLimit>>& limits, int kind);
+                                    const std::vector<std::shared_ptr<RateLimit>>& limits, int kind,
+                                    const std::vector<PeekStatus>* values = nullptr, uint32_t keep = 0);
   void fail(std::vector<std::shared_ptr<PendingCall>>& calls, const std::string& msg);
   void done_calls(size_t n);
 

@@ -15,6 +15,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -93,13 +94,13 @@ namespace {
 enum KernelId {
   KT_FINGERPRINT, KT_HISTOGRAM, KT_HIST_SCAN, KT_SORT_PASS, KT_SCAN, KT_LEADER, KT_DECIDE, KT_FALLBACK, KT_MEMSET,
   KT_CAND, KT_V4_HIST, KT_V4_SCAN, KT_V4_PLACE, KT_V4_GROUP, KT_RESOLVE, KT_RULE_STATS, KT_CACHE_STATS, KT_CENSUS,
-  KT_SET_INDEX, KT_SET_PLAN, KT_SET_APPLY, KT_COUNT
+  KT_SET_INDEX, KT_SET_PLAN, KT_SET_APPLY, KT_SET_INDEX_ROUTED, KT_COUNT
 };
 const char* const kKernelNames[KT_COUNT] = {"k_fingerprint", "k_histogram", "k_hist_scan", "k_sort_pass", "k_scan",
                                             "k_leader",      "k_decide",    "fallback",    "memset",      "k_cand_state",
                                             "k4_hist",       "k4_scan",     "k4_place",    "k4_group",
                                             "k_resolve",     "k_rule_stats", "k_cache_stats", "k_census",
-                                            "k_set_index",   "k_set_plan",  "k_set_apply"};
+                                            "k_set_index",   "k_set_plan",  "k_set_apply", "k_set_index_routed"};
 
 enum Mode { MODE_LSD = 1, MODE_LSD_FULL = 2, MODE_V4 = 4 };
 
@@ -168,6 +169,16 @@ struct rl_engine {
   rl_peek_reply* d_set_vals = nullptr;
   SetCtl* h_set_ctl = nullptr;
   int set_ensure();
+  // a routed set's plan between rl_set_routed_plan and rl_set_routed_commit: its records, its
+  // scratch view, its window generation per region. While it is open the engine refuses what an
+  // open restore refuses (set_busy).
+  bool set_open = false;
+  uint32_t set_plan_n = 0;
+  SetScratch set_plan_sc{};
+  uint32_t set_plan_gen[8] = {};
+  int set_busy(const char* what) {
+    return set_open ? fail(RL_ESTATE, "%s while a routed set plan is open (call rl_set_routed_commit)", what) : 0;
+  }
   // what is folded in behind a batch: COUNT_RULE (k_rule_stats) | COUNT_CACHE (k_cache_stats)
   enum : uint32_t { COUNT_RULE = 1u, COUNT_CACHE = 2u };
   int count_batch(const rl_batch& b, const rl_status* out, const EngineCtl* ctl, uint32_t which);
@@ -958,6 +969,7 @@ int rl_engine::finish(rl_status* out_into, uint32_t* thr_into, bool into) {
 
 int rl_engine::check_batch(const rl_batch* b, bool host) {
   if (restoring) return fail(RL_ESTATE, "submit between rl_restore_begin and rl_restore_end");
+  if (int rc = set_busy("submit")) return rc;
   if (b->n_desc > cfg.max_batch_desc || b->n_req > cfg.max_batch_req || (host && b->blob_bytes > cfg.max_blob_bytes))
     return fail(RL_ECAPACITY, "batch exceeds engine capacity (%u desc, %u req, %u blob bytes)", cfg.max_batch_desc,
                 cfg.max_batch_req, cfg.max_blob_bytes);
@@ -979,6 +991,7 @@ int rl_engine::check_batch(const rl_batch* b, bool host) {
 int rl_engine::submit_common(const rl_batch& d, rl_status* out, uint32_t* thr, RReply* reply, hipEvent_t in_ev,
                              bool inputs_ready, bool host, rl_status* user_out, uint32_t* user_thr, bool raw) {
   if (restoring) return fail(RL_ESTATE, "submit between rl_restore_begin and rl_restore_end");
+  if (int rc = set_busy("submit")) return rc;
   const uint32_t s = (uint32_t)(sub_seq % HSLOTS);
   h_ctl = h_ctl_s[s];
   h_cand = h_cand_s[s];
@@ -1056,6 +1069,8 @@ int rlx_engine_view(rl_engine* e, EngineView* v) {
   v->device = e->cfg.device;
   v->max_batch_desc = e->cfg.max_batch_desc;
   v->stream = e->stream;
+  v->h_rules = e->h_rules.data();
+  v->per_second_split = e->tab.split ? 1 : 0;
   return 0;
 }
 void rlx_engine_hot(rl_engine* e, std::vector<HotKey>& out) { out = e->hot; }
@@ -1879,6 +1894,7 @@ int rl_reset(rl_engine* e) {
   if (e->n_fl) return e->fail(RL_ESTATE, "rl_reset while a batch is in flight");
   e->snap_close();
   e->restoring = false;
+  e->set_open = false;
   return e->clear_table();
 }
 
@@ -1916,6 +1932,7 @@ int rl_snapshot_begin(rl_engine* e, rl_snapshot_header* out) {
   if (!e || !out) return RL_EINVAL;
   if (e->n_fl) return e->fail(RL_ESTATE, "rl_snapshot_begin while a batch is in flight (call rl_wait)");
   if (e->restoring) return e->fail(RL_ESTATE, "rl_snapshot_begin between rl_restore_begin and rl_restore_end");
+  if (int rc = e->set_busy("rl_snapshot_begin")) return rc;
   if (e->snap_open) return e->fail(RL_ESTATE, "a snapshot is open (call rl_snapshot_end)");
   int rc = e->snap_alloc();
   if (rc) return rc;
@@ -2008,6 +2025,7 @@ int rl_restore_begin(rl_engine* e, const rl_snapshot_header* h) {
   if (!e || !h) return RL_EINVAL;
   if (e->n_fl) return e->fail(RL_ESTATE, "rl_restore_begin while a batch is in flight (call rl_wait)");
   if (e->restoring) return e->fail(RL_ESTATE, "a restore is open (call rl_restore_end)");
+  if (int rc = e->set_busy("rl_restore_begin")) return rc;
   if (memcmp(h->magic, kSnapMagic, 8)) return e->fail(RL_EINVAL, "snapshot header: bad magic");
   if (h->header_bytes != RL_SNAP_HEADER_BYTES || h->record_bytes != RL_SNAP_RECORD_BYTES)
     return e->fail(RL_EINVAL, "snapshot header: header / record size %u / %u, expected %u / %u", h->header_bytes,
@@ -2128,6 +2146,7 @@ int rl_resize(rl_engine* e, const uint32_t log2_slots[4]) {
   if (!e || !log2_slots) return RL_EINVAL;
   if (e->n_fl) return e->fail(RL_ESTATE, "rl_resize while a batch is in flight (call rl_wait)");
   if (e->restoring) return e->fail(RL_ESTATE, "rl_resize between rl_restore_begin and rl_restore_end");
+  if (int rc = e->set_busy("rl_resize")) return rc;
   uint32_t lg4[4];
   for (int u = 0; u < 4; ++u) {
     lg4[u] = log2_slots[u] ? log2_slots[u] : e->cfg.log2_slots[u];
@@ -2211,6 +2230,7 @@ int rl_resize(rl_engine* e, const uint32_t log2_slots[4]) {
 static int peek_enter(rl_engine* e, const rl_batch* b, const char* what, bool host) {
   if (e->n_fl) return e->fail(RL_ESTATE, "%s while a batch is in flight (call rl_wait)", what);
   if (e->restoring) return e->fail(RL_ESTATE, "%s between rl_restore_begin and rl_restore_end", what);
+  if (int rc = e->set_busy(what)) return rc;
   if (b->n_desc > e->cfg.max_batch_desc || b->n_req > e->cfg.max_batch_req ||
       (host && b->blob_bytes > e->cfg.max_blob_bytes))
     return e->fail(RL_ECAPACITY, "%s: batch exceeds engine capacity (%u desc, %u req, %u blob bytes)", what,
@@ -2336,6 +2356,97 @@ int rl_engine::set_ensure() {
   return 0;
 }
 
+// The two halves every set runs, the host form (rl_set) and the record form (rl_set_routed_plan /
+// rl_set_routed_commit) alike. gcall: the call's window generation per region (0: writes nothing
+// there); `what` names the entry point in the messages.
+
+// No generation of the call is over: each is the region's newest, or newer, or a lag region's newest - 2.
+static int set_gen_check(rl_engine* e, const char* what, const uint32_t gcall[8]) {
+  for (int r = 0; r < 8; ++r) {
+    const uint32_t G = gcall[r], og = e->occ[r].gen;  // nothing is in flight: the mirror's are the table's
+    if (G && G < og && !(lazy_region(e->tab.lag, (uint32_t)r) && G + 2u == og))
+      return e->fail(RL_EINVAL, "%s: window generation %u of table region %d is over (the region's newest is %u)",
+                     what, G, r, og);
+  }
+  return 0;
+}
+
+// Zero the call's index and control block, run `index` (the form's index kernel, timed under kt)
+// behind `lookup` (its reply pass, may launch nothing) and k_set_plan behind both, and bring the
+// control block to the host. Synchronises the engine stream. Nothing is written to the table.
+static int set_plan_run(rl_engine* e, const char* what, uint32_t n, SetScratch& sc, int kt,
+                        const std::function<void()>& lookup, const std::function<void(const SetScratch&)>& index) {
+  sc = e->set_sc;
+  sc.log2_entries = 6;
+  while ((1ull << sc.log2_entries) < 2ull * n) ++sc.log2_entries;  // <= the allocation's: n <= max_batch_desc
+  hipError_t he = hipMemsetAsync(sc.index, 0, sizeof(SetEntry) << sc.log2_entries, e->stream);
+  if (he == hipSuccess) he = hipMemsetAsync(sc.ctl, 0, sizeof(SetCtl), e->stream);
+  if (he == hipSuccess) {
+    // the replies first: the state before the call, for every duplicate
+    lookup();
+    e->timed(kt, [&] { index(sc); });
+    e->timed(KT_SET_PLAN, [&] { launch_set_plan(e->stream, n, e->tab, sc); });
+    he = hipGetLastError();
+  }
+  if (he == hipSuccess) he = hipMemcpyAsync(e->h_set_ctl, sc.ctl, sizeof(SetCtl), hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  if (he != hipSuccess) return e->hip_fail(he, (std::string(what) + " (nothing written)").c_str());
+  if (e->timing) e->fold_marks();
+  return 0;
+}
+
+// What the plan found on the device: one identity per index entry, the claims per region against
+// the load limits.
+static int set_plan_check(rl_engine* e, const char* what, const uint32_t gcall[8]) {
+  const SetCtl* hc = e->h_set_ctl;
+  if (hc->err & SET_ERR_MIXED)
+    return e->fail(RL_EDEVICE, "%s: two key strings of the call share one 64-bit sort key: split the call "
+                               "(nothing written)", what);
+  if (hc->err) return e->fail(RL_EDEVICE, "%s: the call's index overflowed (nothing written)", what);
+  for (int r = 0; r < 8; ++r) {
+    const uint32_t c = hc->plan[r][0];
+    if (!c) continue;
+    const uint64_t live = region_live(e->occ[r], lazy_region(e->tab.lag, (uint32_t)r), gcall[r]);
+    if (live + c > e->occ[r].limit)
+      return e->fail(RL_ENOSPC, "%s: table region %d holds %llu live slots and the call claims %u, over its load "
+                                "limit of %u (nothing written)", what, r, (unsigned long long)live, c, e->occ[r].limit);
+  }
+  return 0;
+}
+
+// The applying pass over a checked plan, then the occupancy into the mirror and onto the device as
+// rl_resize publishes it. out (host, nullable): the n replies at d_rep are copied there.
+static int set_apply(rl_engine* e, const char* what, uint32_t n, const SetScratch& sc, const uint32_t gcall[8],
+                     rl_peek_reply* out, const rl_peek_reply* d_rep) {
+  const SetCtl* hc = e->h_set_ctl;
+  e->timed(KT_SET_APPLY, [&] { launch_set_apply(e->stream, n, e->tab, sc); });
+  hipError_t he = hipGetLastError();
+  if (he == hipSuccess) he = hipMemcpyAsync(e->h_set_ctl, sc.ctl, sizeof(SetCtl), hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess && out)
+    he = hipMemcpyAsync(out, d_rep, (size_t)n * sizeof(rl_peek_reply), hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  if (he != hipSuccess) return e->hip_fail(he, (std::string(what) + ": applying pass (the table may hold part of the call)").c_str());
+  if (e->timing) e->fold_marks();
+  if (hc->err)
+    return e->fail(RL_EDEVICE, "%s: a region had no free slot left (the table may hold part of the call)", what);
+  RegionOcc nocc[8];
+  uint64_t claims = 0;
+  for (int r = 0; r < 8; ++r) {
+    nocc[r] = e->occ[r];
+    const uint32_t c = hc->claim[r][0];
+    if (c) occ_advance(nocc[r], lazy_region(e->tab.lag, (uint32_t)r), gcall[r], c);
+    claims += c;
+  }
+  if (claims) {
+    he = hipMemcpy(e->d_occ, nocc, sizeof nocc, hipMemcpyHostToDevice);
+    if (he != hipSuccess) return e->hip_fail(he, (std::string(what) + ": publish occupancy").c_str());
+    memcpy(e->occ, nocc, sizeof nocc);
+    e->st.inserted_keys += claims;
+    e->st.live_keys = e->live_total();
+  }
+  return 0;
+}
+
 // rl_set: every check first (host: shape, values, window generations; device: one identity per
 // index entry, the claims per region against the load limits), then the applying pass, then the
 // occupancy into the mirror and onto the device as rl_resize publishes it.
@@ -2373,12 +2484,8 @@ int rl_set(rl_engine* e, const rl_batch* b, const rl_peek_reply* values, rl_peek
                                 "one call: split the call", i, pl.gen, gcall[pl.region], pl.region);
     gcall[pl.region] = pl.gen;
   }
-  for (int r = 0; r < 8; ++r) {
-    const uint32_t G = gcall[r], og = e->occ[r].gen;  // nothing is in flight: the mirror's are the table's
-    if (G && G < og && !(lazy_region(e->tab.lag, (uint32_t)r) && G + 2u == og))
-      return e->fail(RL_EINVAL, "rl_set: window generation %u of table region %d is over (the region's newest is %u)",
-                     G, r, og);
-  }
+  rc = set_gen_check(e, "rl_set", gcall);
+  if (rc) return rc;
   if (!b->n_desc) return 0;
   rc = e->set_ensure();
   if (rc) return rc;
@@ -2386,64 +2493,88 @@ int rl_set(rl_engine* e, const rl_batch* b, const rl_peek_reply* values, rl_peek
   rl_peek_reply* d_rep = nullptr;
   rc = peek_stage(e, b, d, d_rep);
   if (rc) return rc;
-  SetScratch sc = e->set_sc;
-  sc.log2_entries = 6;
-  while ((1ull << sc.log2_entries) < 2ull * b->n_desc) ++sc.log2_entries;  // <= the allocation's: n_desc <= max_batch_desc
-  const size_t nbytes = (size_t)b->n_desc * sizeof(rl_peek_reply);
-  hipError_t he = hipMemcpyAsync(e->d_set_vals, values, nbytes, hipMemcpyHostToDevice, e->stream);
-  if (he == hipSuccess) he = hipMemsetAsync(sc.index, 0, sizeof(SetEntry) << sc.log2_entries, e->stream);
-  if (he == hipSuccess) he = hipMemsetAsync(sc.ctl, 0, sizeof(SetCtl), e->stream);
-  if (he == hipSuccess) {
-    // the replies first: the state before the call, for every duplicate
-    if (out) launch_peek(e->stream, d, e->d_rules, e->n_rules, e->cfg.hash_seed, e->tab, d_rep, false);
-    e->timed(KT_SET_INDEX, [&] {
-      launch_set_index(e->stream, d, e->d_rules, e->n_rules, e->cfg.hash_seed, e->tab, e->d_set_vals, sc);
-    });
-    e->timed(KT_SET_PLAN, [&] { launch_set_plan(e->stream, b->n_desc, e->tab, sc); });
-    he = hipGetLastError();
-  }
-  if (he == hipSuccess) he = hipMemcpyAsync(e->h_set_ctl, sc.ctl, sizeof(SetCtl), hipMemcpyDeviceToHost, e->stream);
-  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  const hipError_t he = hipMemcpyAsync(e->d_set_vals, values, (size_t)b->n_desc * sizeof(rl_peek_reply),
+                                       hipMemcpyHostToDevice, e->stream);
   if (he != hipSuccess) return e->hip_fail(he, "rl_set (nothing written)");
-  if (e->timing) e->fold_marks();
-  const SetCtl* hc = e->h_set_ctl;
-  if (hc->err & SET_ERR_MIXED)
-    return e->fail(RL_EDEVICE, "rl_set: two key strings of the call share one 64-bit sort key: split the call "
-                               "(nothing written)");
-  if (hc->err) return e->fail(RL_EDEVICE, "rl_set: the call's index overflowed (nothing written)");
-  for (int r = 0; r < 8; ++r) {
-    const uint32_t c = hc->plan[r][0];
-    if (!c) continue;
-    const uint64_t live = region_live(e->occ[r], lazy_region(e->tab.lag, (uint32_t)r), gcall[r]);
-    if (live + c > e->occ[r].limit)
-      return e->fail(RL_ENOSPC, "rl_set: table region %d holds %llu live slots and the call claims %u, over its load "
-                                "limit of %u (nothing written)", r, (unsigned long long)live, c, e->occ[r].limit);
+  SetScratch sc;
+  rc = set_plan_run(
+      e, "rl_set", b->n_desc, sc, KT_SET_INDEX,
+      [&] {
+        if (out) launch_peek(e->stream, d, e->d_rules, e->n_rules, e->cfg.hash_seed, e->tab, d_rep, false);
+      },
+      [&](const SetScratch& s) {
+        launch_set_index(e->stream, d, e->d_rules, e->n_rules, e->cfg.hash_seed, e->tab, e->d_set_vals, s);
+      });
+  if (!rc) rc = set_plan_check(e, "rl_set", gcall);
+  if (rc) return rc;
+  return set_apply(e, "rl_set", b->n_desc, sc, gcall, out, d_rep);
+}
+
+// Routed set, the engine's two phases (rl_hip.h "Routed set"). The plan is rl_set's checking half
+// over records that arrived from every origin: what rl_set's host checks refuse is found by
+// k_set_index_routed and read here from the control block.
+int rl_set_routed_plan(rl_engine* e, const void* d_records, const rl_peek_reply* d_values, uint32_t n,
+                       rl_peek_reply* d_reply_or_null) {
+  if (!e) return RL_EINVAL;
+  const char* what = "rl_set_routed_plan";
+  if (e->n_fl) return e->fail(RL_ESTATE, "%s while a batch is in flight (call rl_wait)", what);
+  if (e->restoring) return e->fail(RL_ESTATE, "%s between rl_restore_begin and rl_restore_end", what);
+  if (e->set_open) return e->fail(RL_ESTATE, "%s: a plan is open (call rl_set_routed_commit)", what);
+  if (e->cfg.max_batch_desc > SET_MAX_DESC)
+    return e->fail(RL_ECAPACITY, "%s: max_batch_desc %u above 2^29", what, e->cfg.max_batch_desc);
+  if (n > e->cfg.max_batch_desc)
+    return e->fail(RL_ECAPACITY, "%s: %u records exceed max_batch_desc %u", what, n, e->cfg.max_batch_desc);
+  if (n && (!d_records || !d_values)) return e->fail(RL_EINVAL, "%s: null record or value array", what);
+  if (!e->d_rules) {
+    const int rc = rl_load_rules(e, nullptr, 0);
+    if (rc) return rc;
   }
-  e->timed(KT_SET_APPLY, [&] { launch_set_apply(e->stream, b->n_desc, e->tab, sc); });
-  he = hipGetLastError();
-  if (he == hipSuccess) he = hipMemcpyAsync(e->h_set_ctl, sc.ctl, sizeof(SetCtl), hipMemcpyDeviceToHost, e->stream);
-  if (he == hipSuccess && out) he = hipMemcpyAsync(out, d_rep, nbytes, hipMemcpyDeviceToHost, e->stream);
-  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-  if (he != hipSuccess) return e->hip_fail(he, "rl_set: applying pass (the table may hold part of the call)");
-  if (e->timing) e->fold_marks();
-  if (hc->err)
-    return e->fail(RL_EDEVICE, "rl_set: a region had no free slot left (the table may hold part of the call)");
-  RegionOcc nocc[8];
-  uint64_t claims = 0;
-  for (int r = 0; r < 8; ++r) {
-    nocc[r] = e->occ[r];
-    const uint32_t c = hc->claim[r][0];
-    if (c) occ_advance(nocc[r], lazy_region(e->tab.lag, (uint32_t)r), gcall[r], c);
-    claims += c;
+  uint32_t gcall[8] = {};
+  if (n) {
+    int rc = e->set_ensure();
+    if (rc) return rc;
+    const RRec* recs = reinterpret_cast<const RRec*>(d_records);
+    rc = set_plan_run(
+        e, what, n, e->set_plan_sc, KT_SET_INDEX_ROUTED,
+        [&] {
+          if (d_reply_or_null)
+            launch_peek_routed(e->stream, recs, n, e->d_rules, e->n_rules, e->tab, d_reply_or_null, false);
+        },
+        [&](const SetScratch& s) {
+          launch_set_index_routed(e->stream, recs, d_values, n, e->d_rules, e->n_rules, e->tab, s);
+        });
+    if (rc) return rc;
+    const SetCtl* hc = e->h_set_ctl;
+    if (hc->err & SET_ERR_BADREC)
+      return e->fail(RL_EINVAL, "%s: a record's rule id is unknown or its time is above 0xFFFD0000 (nothing written)",
+                     what);
+    if (hc->err & SET_ERR_BADVAL)
+      return e->fail(RL_EINVAL, "%s: a value has ttl_s or cached_s zero, or its sum with the time is not below 2^32 "
+                                "(nothing written)", what);
+    for (int r = 0; r < 8; ++r) {
+      const uint32_t hi = hc->gen_max[r][0], lo = ~hc->gen_minc[r][0];
+      if (!hi) continue;
+      if (lo != hi)
+        return e->fail(RL_EINVAL, "%s: two window generations (%u and %u) of table region %d in one call: split the "
+                                  "call (nothing written)", what, lo, hi, r);
+      gcall[r] = hi;
+    }
+    rc = set_gen_check(e, what, gcall);
+    if (!rc) rc = set_plan_check(e, what, gcall);
+    if (rc) return rc;
   }
-  if (claims) {
-    he = hipMemcpy(e->d_occ, nocc, sizeof nocc, hipMemcpyHostToDevice);
-    if (he != hipSuccess) return e->hip_fail(he, "rl_set: publish occupancy");
-    memcpy(e->occ, nocc, sizeof nocc);
-    e->st.inserted_keys += claims;
-    e->st.live_keys = e->live_total();
-  }
+  e->set_open = true;
+  e->set_plan_n = n;
+  memcpy(e->set_plan_gen, gcall, sizeof gcall);
   return 0;
+}
+
+int rl_set_routed_commit(rl_engine* e, int apply) {
+  if (!e) return RL_EINVAL;
+  if (!e->set_open) return e->fail(RL_ESTATE, "rl_set_routed_commit without an open plan (call rl_set_routed_plan)");
+  e->set_open = false;
+  if (!apply || !e->set_plan_n) return 0;
+  return set_apply(e, "rl_set_routed_commit", e->set_plan_n, e->set_plan_sc, e->set_plan_gen, nullptr, nullptr);
 }
 
 int rl_peek_device(rl_engine* e, const rl_batch* b, rl_peek_reply* d_out) {
@@ -2465,6 +2596,7 @@ int rl_peek_routed(rl_engine* e, const void* d_records, uint32_t n, rl_peek_repl
   const bool forget = (flags & RL_PEEK_ROUTED_FORGET) != 0;
   if (e->n_fl) return e->fail(RL_ESTATE, "rl_peek_routed while a batch is in flight (call rl_wait)");
   if (e->restoring) return e->fail(RL_ESTATE, "rl_peek_routed between rl_restore_begin and rl_restore_end");
+  if (int rc = e->set_busy("rl_peek_routed")) return rc;
   if (n && (!d_records || (!forget && !d_reply))) return e->fail(RL_EINVAL, "rl_peek_routed: null record or reply array");
   if (!e->d_rules) {
     const int rc = rl_load_rules(e, nullptr, 0);
@@ -2506,6 +2638,7 @@ int rl_rule_stats_read(rl_engine* e, uint32_t first_rule, uint32_t n, rl_rule_st
   if (!e) return RL_EINVAL;
   if (e->n_fl) return e->fail(RL_ESTATE, "rl_rule_stats_read while a batch is in flight (call rl_wait)");
   if (e->restoring) return e->fail(RL_ESTATE, "rl_rule_stats_read between rl_restore_begin and rl_restore_end");
+  if (int rc = e->set_busy("rl_rule_stats_read")) return rc;
   if (flags & ~(uint32_t)RL_RULE_STATS_CLEAR) return e->fail(RL_EINVAL, "unknown rl_rule_stats_read flags 0x%x", flags);
   if ((uint64_t)first_rule + n > e->n_rules)
     return e->fail(RL_EINVAL, "rl_rule_stats_read: rules [%u, %llu) of %u loaded", first_rule,
@@ -2538,6 +2671,7 @@ int rl_cache_stats_read(rl_engine* e, rl_cache_stats* out, uint32_t flags) {
   if (!e) return RL_EINVAL;
   if (e->n_fl) return e->fail(RL_ESTATE, "rl_cache_stats_read while a batch is in flight (call rl_wait)");
   if (e->restoring) return e->fail(RL_ESTATE, "rl_cache_stats_read between rl_restore_begin and rl_restore_end");
+  if (int rc = e->set_busy("rl_cache_stats_read")) return rc;
   if (flags & ~(uint32_t)RL_CACHE_STATS_CLEAR) return e->fail(RL_EINVAL, "unknown rl_cache_stats_read flags 0x%x", flags);
   if (!out) return e->fail(RL_EINVAL, "rl_cache_stats_read: null output");
   memset(out, 0, sizeof *out);
@@ -2561,6 +2695,7 @@ int rl_census(rl_engine* e, int64_t now, rl_census_report* out) {
   if (now < 0 || now > MAX_NOW) return e->fail(RL_EINVAL, "rl_census: time %lld outside [0, 0xFFFD0000]", (long long)now);
   if (e->n_fl) return e->fail(RL_ESTATE, "rl_census while a batch is in flight (call rl_wait)");
   if (e->restoring) return e->fail(RL_ESTATE, "rl_census between rl_restore_begin and rl_restore_end");
+  if (int rc = e->set_busy("rl_census")) return rc;
   hipError_t he = hipSuccess;
   if (!e->d_census) {
     he = hipMalloc(&e->d_census, sizeof(CensusCtl));

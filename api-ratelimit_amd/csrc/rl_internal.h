@@ -49,6 +49,9 @@ struct EngineView {
   int device;
   uint32_t max_batch_desc;
   hipStream_t stream;  // the engine stream (rl_peek_routed / rl_route_unpack_peek run on it)
+  // what rl_set's per-value host checks read (rl_router_set runs them at the origin)
+  const DevRule* h_rules;  // host copy of rules[0, n_rules); valid until rules are loaded or appended
+  int per_second_split;
 };
 int rlx_engine_view(rl_engine* e, EngineView* v);
 // A router's engine keeps SECOND key strings findable up to 3 s behind its newest time

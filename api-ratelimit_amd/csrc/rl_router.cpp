@@ -54,6 +54,7 @@
 #include "rl_common.h"
 #include "rl_hip.h"
 #include "rl_internal.h"
+#include "rl_set.h"
 
 using namespace rlhip;
 
@@ -321,6 +322,14 @@ struct EmuXport : Xport {
   }
 };
 
+// The routed by-key calls (rl_router_peek / _forget / _set): one origin / exchange / owner /
+// reply sequence, differing in the owner's work (and, for a set, the values beside the records
+// and the plan-status exchange ahead of any write).
+enum ByKeyOp { OP_PEEK, OP_FORGET, OP_SET };
+const char* op_name(ByKeyOp op) {
+  return op == OP_SET ? "rl_router_set" : op == OP_FORGET ? "rl_router_forget" : "rl_router_peek";
+}
+
 // One owner run: consecutive origins' records (compact by origin) whose times fit one engine batch.
 struct Run {
   uint32_t off, n;
@@ -416,6 +425,12 @@ struct Shard {
   rl_peek_reply* pk_back = nullptr;
   uint8_t* pk_h_in = nullptr;
   uint8_t* pk_d_in = nullptr;
+  // routed set (allocated at its first call): the origin's values in descriptor order (pinned +
+  // device staging), then laid out like the strided record buffer; the owner's values beside recv
+  rl_peek_reply* sv_h = nullptr;
+  rl_peek_reply* sv_d = nullptr;
+  rl_peek_reply* sv_send = nullptr;
+  rl_peek_reply* sv_recv = nullptr;
 };
 
 struct StepSlot {
@@ -533,9 +548,11 @@ struct rl_router {
   int peek_validate(const rl_batch& b, uint32_t n_rules, std::string& why) const;
   int peek_alloc(Shard& S);
   int peek_stage(uint32_t s, uint32_t k, const rl_batch& hb, rl_batch& db);
-  int peek(const rl_batch* batches, rl_peek_reply* const* out, bool forget);
-  int peek_coll(uint32_t k, rl_peek_reply* const* out, bool forget);
-  int peek_local(uint32_t k, rl_peek_reply* const* out, bool forget);
+  int set_validate(const Shard& S, const rl_batch& b, const rl_peek_reply* values, std::string& why) const;
+  int set_alloc(Shard& S);
+  int peek(const rl_batch* batches, rl_peek_reply* const* out, ByKeyOp op, const rl_peek_reply* const* values = nullptr);
+  int peek_coll(uint32_t k, rl_peek_reply* const* out, ByKeyOp op);
+  int peek_local(uint32_t k, rl_peek_reply* const* out, ByKeyOp op);
   void note_combine(uint32_t s, uint32_t k);
   void refresh_hot();
   int check_config();
@@ -563,9 +580,10 @@ void rl_router::free_all() {
       for (void* p : {(void*)t.h_x, (void*)t.hs.h_in, (void*)t.hs.h_out, (void*)t.hs.h_thr})
         if (p) (void)hipHostFree(p);
     }
-    for (void* p : {(void*)s.pk_reply, (void*)s.pk_back, (void*)s.pk_d_in})
+    for (void* p : {(void*)s.pk_reply, (void*)s.pk_back, (void*)s.pk_d_in, (void*)s.sv_d, (void*)s.sv_send, (void*)s.sv_recv})
       if (p) (void)hipFree(p);
     if (s.pk_h_in) (void)hipHostFree(s.pk_h_in);
+    if (s.sv_h) (void)hipHostFree(s.sv_h);
     if (s.d_hot) (void)hipFree(s.d_hot);
     if (s.h_hot) (void)hipHostFree(s.h_hot);
     if (s.ev_hot) (void)hipEventDestroy(s.ev_hot);
@@ -1590,8 +1608,53 @@ int rl_router::peek_stage(uint32_t s, uint32_t k, const rl_batch& b, rl_batch& d
   return 0;
 }
 
-int rl_router::peek(const rl_batch* batches, rl_peek_reply* const* out, bool forget) {
-  const char* what = forget ? "rl_router_forget" : "rl_router_peek";
+// rl_set's per-value host checks, at the origin (the parts a descriptor writes).
+int rl_router::set_validate(const Shard& S, const rl_batch& b, const rl_peek_reply* values, std::string& why) const {
+  if (b.n_desc && !values) {
+    why = "null value array";
+    return RL_EINVAL;
+  }
+  char buf[128];
+  for (uint32_t i = 0; i < b.n_desc; ++i) {
+    if (b.rule_id[i] == RL_NIL_RULE) continue;
+    const rl_peek_reply& v = values[i];
+    const bool wc = !(v.flags & RL_SET_KEEP_COUNTER);
+    const bool wf = !(v.flags & RL_SET_KEEP_CACHE) && S.v.local_cache;
+    const bool ps = S.v.per_second_split && S.v.h_rules[b.rule_id[i]].unit == RL_UNIT_SECOND;
+    const uint64_t t = (uint64_t)b.now[b.req_of[i]];
+    const char* bad = nullptr;
+    if (wc && (v.flags & RL_PEEK_FOUND) && !ps) {
+      if (!v.ttl_s) bad = "a found main-store value with ttl_s == 0";
+      else if (t + v.ttl_s >= (1ull << 32)) bad = "time + ttl_s is not below 2^32";
+    }
+    if (!bad && wf && (v.flags & RL_PEEK_LOCAL_CACHED)) {
+      if (!v.cached_s) bad = "a cached value with cached_s == 0";
+      else if (t + v.cached_s >= (1ull << 32)) bad = "time + cached_s is not below 2^32";
+    }
+    if (bad) {
+      snprintf(buf, sizeof buf, "descriptor %u: %s", i, bad);
+      why = buf;
+      return RL_EINVAL;
+    }
+  }
+  return 0;
+}
+
+int rl_router::set_alloc(Shard& S) {
+  if (S.sv_h && S.sv_d && S.sv_send && S.sv_recv) return 0;
+  const size_t d = (size_t)cfg.max_desc * sizeof(rl_peek_reply), n = d * cfg.n_shards;
+  hipError_t he = hipSuccess;
+  if (!S.sv_h) he = hipHostMalloc(&S.sv_h, d, hipHostMallocDefault);
+  if (he == hipSuccess && !S.sv_d) he = hipMalloc(&S.sv_d, d);
+  if (he == hipSuccess && !S.sv_send) he = hipMalloc(&S.sv_send, n);
+  if (he == hipSuccess && !S.sv_recv) he = hipMalloc(&S.sv_recv, n);
+  return he == hipSuccess ? 0 : RL_EHIP;
+}
+
+// The origin half of every by-key call, then the transport's half. values: a set's, per engine.
+int rl_router::peek(const rl_batch* batches, rl_peek_reply* const* out, ByKeyOp op,
+                    const rl_peek_reply* const* values) {
+  const char* what = op_name(op);
   if (broken) return fail(RL_ECOMM, "the router's communicator was aborted after a transport failure");
   if (done != seq) return fail(RL_ESTATE, "%s with a routed step in flight: call rl_router_wait", what);
   const uint32_t k = (uint32_t)((seq + 1) % NSLOT), nl = n_local();
@@ -1608,29 +1671,45 @@ int rl_router::peek(const rl_batch* batches, rl_peek_reply* const* out, bool for
     int rc = rlx_engine_view(S.e, &S.v);  // (rules may have been appended since)
     if (rc) t.msg = rl_last_error(S.e);
     if (!rc) rc = peek_validate(batches[s], S.v.n_rules, t.msg);
-    if (!rc && !forget && batches[s].n_desc && (!out || !out[s])) {
+    if (!rc && op == OP_PEEK && batches[s].n_desc && (!out || !out[s])) {
       rc = RL_EINVAL;
       t.msg = "null reply array";
     }
+    if (!rc && op == OP_SET) rc = set_validate(S, batches[s], values[s], t.msg);
     if (!rc && (rc = peek_alloc(S))) t.msg = "reply buffer / staging allocation failed";
+    if (!rc && op == OP_SET && (rc = set_alloc(S))) t.msg = "value buffer / staging allocation failed";
     if (!rc && (rc = peek_stage(s, k, batches[s], t.b))) t.msg = "host staging copy failed";
+    if (!rc && op == OP_SET && batches[s].n_desc) {
+      const size_t nb = (size_t)batches[s].n_desc * sizeof(rl_peek_reply);
+      memcpy(S.sv_h, values[s], nb);
+      if (hipMemcpyAsync(S.sv_d, S.sv_h, nb, hipMemcpyHostToDevice, S.os) != hipSuccess) {
+        rc = RL_EHIP;
+        t.msg = "value staging copy failed";
+      }
+    }
     if (rc) t.b = rl_batch{};
     t.rc_pack = rc;
     pack(s, k, true);
+    if (op == OP_SET && !t.rc_pack && t.b.n_desc) {  // the values to their records' places, behind the pack
+      launch_set_values_pack(S.os, t.b.n_desc, cfg.max_desc * cfg.n_shards, t.pb.perm, S.sv_d, S.sv_send);
+      (void)hipGetLastError();  // (a failed launch shows at the stream's next wait)
+    }
     if (!coll) (void)hipStreamSynchronize(S.os);
   }
-  return coll ? peek_coll(k, out, forget) : peek_local(k, out, forget);
+  return coll ? peek_coll(k, out, op) : peek_local(k, out, op);
 }
 
 static const char* const kPackRefused =
     "route pack: the device refused the batch (unknown rule id or request index, malformed prefix offsets, a time "
     "outside [0, 0xFFFD0000], or its look-back spin limit expired)";
 
-// Collective transports: counts (+ every origin's status), records, the owner's lookup on the
-// engine stream, then its status and the replies back, the origin's unpack on the engine stream.
-// The streams hand over by events; the host waits once, bounded, at the end of each half.
-int rl_router::peek_coll(uint32_t k, rl_peek_reply* const* out, bool forget) {
-  const char* what = forget ? "rl_router_forget" : "rl_router_peek";
+// Collective transports: counts (+ every origin's status), records (a set: and values), the
+// owner's work on the engine stream, then its status and the replies back, the origin's unpack on
+// the engine stream. The streams hand over by events; the host waits, bounded, at the end of each
+// half. A set's owner work is two-phase: the plan, each owner's plan code to every rank (the
+// mechanism of the reply status word), and only if all are zero the commit.
+int rl_router::peek_coll(uint32_t k, rl_peek_reply* const* out, ByKeyOp op) {
+  const char* what = op_name(op);
   const uint32_t G = cfg.n_shards, me = cfg.rank;
   const size_t D = cfg.max_desc;
   Shard& S = sh[0];
@@ -1660,10 +1739,10 @@ int rl_router::peek_coll(uint32_t k, rl_peek_reply* const* out, bool forget) {
   int bad = -1;
   for (uint32_t j = 0; j < G && bad < 0; ++j)
     if (hr[XS * j + 1]) bad = (int)j;
-  if (bad >= 0) {  // every rank saw the same status words: all leave here, nothing looked up or cleared
+  if (bad >= 0) {  // every rank saw the same status words: all leave here, nothing looked up or written
     if (t.rc_pack) return fail(t.rc_pack, "%s: shard %u: %s", what, me, t.msg.c_str());
-    return fail(RL_EPEER, "%s: shard %d refused its batch with %d: nothing was looked up or cleared", what, bad,
-                (int)hr[XS * bad + 1]);
+    return fail(RL_EPEER, "%s: shard %d refused its batch with %d: nothing was looked up or %s", what, bad,
+                (int)hr[XS * bad + 1], op == OP_SET ? "written" : "cleared");
   }
   size_t sc[MAXS], sd[MAXS], rc[MAXS], rd[MAXS];
   uint64_t ro = 0;
@@ -1677,15 +1756,74 @@ int rl_router::peek_coll(uint32_t k, rl_peek_reply* const* out, bool forget) {
     ro += rc[j];
   }
   t.n_in = (uint32_t)(ro / REC);
-  nr = xp->a2av(t.pb.send, sc, sd, t.recv, rc, rd, rs);
+  if (op == OP_SET) {  // the values beside the records: the same count vectors, scaled 16 / 32
+    static_assert(REC == 2 * sizeof(rl_peek_reply), "a value is half a record");
+    size_t vc[MAXS], vd[MAXS], wc[MAXS], wd[MAXS];
+    for (uint32_t j = 0; j < G; ++j) vc[j] = sc[j] / 2, vd[j] = sd[j] / 2, wc[j] = rc[j] / 2, wd[j] = rd[j] / 2;
+    nr = xp->group_start();
+    if (nr == ncclSuccess) nr = xp->a2av(t.pb.send, sc, sd, t.recv, rc, rd, rs);
+    if (nr == ncclSuccess) nr = xp->a2av(S.sv_send, vc, vd, S.sv_recv, wc, wd, rs);
+    const ncclResult_t ne = xp->group_end();
+    if (nr == ncclSuccess) nr = ne;
+  } else {
+    nr = xp->a2av(t.pb.send, sc, sd, t.recv, rc, rd, rs);
+  }
   if (nr != ncclSuccess) return nccl_fail(nr, "all-to-all-v(peek records)");
   // owner: everything received, origin-major, on the engine stream behind the records
   int mine = 0;
   he = hipEventRecord(ev_rs, rs);
-  if (he == hipSuccess) he = hipStreamWaitEvent(es, ev_rs, 0);
-  if (he == hipSuccess) {
-    mine = rl_peek_routed(S.e, t.recv, t.n_in, S.pk_reply, forget ? (uint32_t)RL_PEEK_ROUTED_FORGET : 0u);
+  if (op == OP_SET) {
+    // The plan synchronises the engine stream: the records' arrival is waited for here, bounded,
+    // so that wait never stands behind a collective.
+    if (he == hipSuccess)
+      if (int rcw = wait_bounded(ev_rs, nullptr, "all-to-all-v(set records)", &he)) return rcw;
+    if (he == hipSuccess) {
+      mine = rl_set_routed_plan(S.e, t.recv, S.sv_recv, t.n_in, S.pk_reply);
+      if (mine) t.msg = rl_last_error(S.e);
+    } else {
+      mine = RL_EHIP;
+      t.msg = std::string("record exchange: ") + hipGetErrorString(he);
+    }
+    // every owner's plan code to every rank; any non-zero: every owner drops its plan
+    int32_t* hw = t.h_x + 2 * XS * G;
+    int32_t* hpl = hw + G;
+    for (uint32_t j = 0; j < G; ++j) hw[j] = mine;
+    he = hipMemcpyAsync(t.d_x + 2 * XS * G, hw, 4 * G, hipMemcpyHostToDevice, rs);
+    nr = xp->a2a(t.d_x + 2 * XS * G, t.d_x + 2 * XS * G + G, 4, rs);
+    if (nr != ncclSuccess) {
+      if (!mine) (void)rl_set_routed_commit(S.e, 0);
+      return nccl_fail(nr, "all-to-all(set plan statuses)");
+    }
+    if (he == hipSuccess) he = hipMemcpyAsync(hpl, t.d_x + 2 * XS * G + G, 4 * G, hipMemcpyDeviceToHost, rs);
+    if (he == hipSuccess) he = hipEventRecord(ev_cnt, rs);
+    if (he == hipSuccess) {
+      if (int rcw = wait_bounded(ev_cnt, nullptr, "all-to-all(set plan statuses)", &he)) {
+        if (!mine) (void)rl_set_routed_commit(S.e, 0);
+        return rcw;
+      }
+    }
+    if (he != hipSuccess) {  // the peers' plan codes are unknown: nobody may write
+      if (!mine) (void)rl_set_routed_commit(S.e, 0);
+      abort_comm();
+      return fail(RL_ECOMM, "%s: plan-status exchange: %s (communicator aborted)", what, hipGetErrorString(he));
+    }
+    bad = -1;
+    for (uint32_t j = 0; j < G && bad < 0; ++j)
+      if (hpl[j]) bad = (int)j;
+    if (bad >= 0) {  // every rank saw the same codes: no owner has written anything, out is untouched
+      if (!mine) (void)rl_set_routed_commit(S.e, 0);
+      if (mine) return fail(mine, "%s: shard %u (owner plan): %s", what, me, t.msg.c_str());
+      return fail(RL_EPEER, "%s: owner %d refused its plan with %d: nothing was written anywhere", what, bad,
+                  (int)hpl[bad]);
+    }
+    mine = rl_set_routed_commit(S.e, 1);
     if (mine) t.msg = rl_last_error(S.e);
+  } else {
+    if (he == hipSuccess) he = hipStreamWaitEvent(es, ev_rs, 0);
+    if (he == hipSuccess) {
+      mine = rl_peek_routed(S.e, t.recv, t.n_in, S.pk_reply, op == OP_FORGET ? (uint32_t)RL_PEEK_ROUTED_FORGET : 0u);
+      if (mine) t.msg = rl_last_error(S.e);
+    }
   }
   if (he == hipSuccess) he = hipEventRecord(S.ev, es);
   if (he == hipSuccess) he = hipStreamWaitEvent(rs, S.ev, 0);
@@ -1734,10 +1872,11 @@ int rl_router::peek_coll(uint32_t k, rl_peek_reply* const* out, bool forget) {
     // after a failure to enqueue: drain the exchange stream (bounded), the statuses are lost
     if (int rcw = wait_bounded(nullptr, rs, "all-to-all(peek replies)", nullptr)) return rcw;
   }
-  if (mine) return fail(mine, "%s: shard %u (owner lookup): %s", what, me, t.msg.c_str());
+  if (mine) return fail(mine, "%s: shard %u (owner %s): %s", what, me, op == OP_SET ? "commit" : "lookup", t.msg.c_str());
   if (he != hipSuccess) return fail(RL_EHIP, "%s: reply exchange / unpack: %s", what, hipGetErrorString(he));
   for (uint32_t j = 0; j < G; ++j)
-    if (hst[j]) return fail(RL_EPEER, "%s: owner %u failed its lookup with %d", what, j, (int)hst[j]);
+    if (hst[j])
+      return fail(RL_EPEER, "%s: owner %u failed its %s with %d", what, j, op == OP_SET ? "commit" : "lookup", (int)hst[j]);
   if (rc_un) return fail(rc_un, "%s: unpack: %s", what, rl_last_error(S.e));
   if (out && out[0] && t.b.n_desc) {
     he = hipMemcpy(out[0], d_out, (size_t)t.b.n_desc * sizeof(rl_peek_reply), hipMemcpyDeviceToHost);
@@ -1747,8 +1886,8 @@ int rl_router::peek_coll(uint32_t k, rl_peek_reply* const* out, bool forget) {
 }
 
 // Local transport: the same exchanges by device copies, the owners one after another.
-int rl_router::peek_local(uint32_t k, rl_peek_reply* const* out, bool forget) {
-  const char* what = forget ? "rl_router_forget" : "rl_router_peek";
+int rl_router::peek_local(uint32_t k, rl_peek_reply* const* out, ByKeyOp op) {
+  const char* what = op_name(op);
   const uint32_t G = cfg.n_shards;
   const size_t D = cfg.max_desc;
   for (uint32_t s = 0; s < G; ++s) {
@@ -1764,7 +1903,7 @@ int rl_router::peek_local(uint32_t k, rl_peek_reply* const* out, bool forget) {
       t.msg = kPackRefused;
     }
   }
-  for (uint32_t s = 0; s < G; ++s)  // nothing looked up or cleared anywhere
+  for (uint32_t s = 0; s < G; ++s)  // nothing looked up, cleared or written anywhere
     if (sh[s].st[k].rc_pack) return fail(sh[s].st[k].rc_pack, "%s: shard %u: %s", what, s, sh[s].st[k].msg.c_str());
   hipError_t he = hipSuccess;
   for (uint32_t j = 0; j < G; ++j) {  // owner j: origin 0's section j, then origin 1's, ...
@@ -1776,18 +1915,49 @@ int rl_router::peek_local(uint32_t k, rl_peek_reply* const* out, bool forget) {
       tj.rcv[i] = c;
       if (c && he == hipSuccess)
         he = hipMemcpyAsync(tj.recv + o, sh[i].st[k].pb.send + j * D, (size_t)c * REC, hipMemcpyDeviceToDevice, rs);
+      if (c && he == hipSuccess && op == OP_SET)
+        he = hipMemcpyAsync(sh[j].sv_recv + o, sh[i].sv_send + j * D, (size_t)c * sizeof(rl_peek_reply),
+                            hipMemcpyDeviceToDevice, rs);
       o += c;
     }
     tj.n_in = (uint32_t)o;
   }
   if (he == hipSuccess) he = hipStreamSynchronize(rs);
   if (he != hipSuccess) return fail(RL_EHIP, "%s: record exchange: %s", what, hipGetErrorString(he));
-  for (uint32_t j = 0; j < G; ++j) {
-    ShardStep& t = sh[j].st[k];
-    const int rc = rl_peek_routed(sh[j].e, t.recv, t.n_in, sh[j].pk_reply, forget ? (uint32_t)RL_PEEK_ROUTED_FORGET : 0u);
-    if (rc) return fail(rc, "%s: shard %u (owner lookup): %s", what, j, rl_last_error(sh[j].e));
-    he = hipStreamSynchronize(sh[j].v.stream);
-    if (he != hipSuccess) return fail(RL_EHIP, "%s: shard %u (owner lookup): %s", what, j, hipGetErrorString(he));
+  if (op == OP_SET) {
+    // every owner plans; the first failing shard's code ends the call with every plan dropped:
+    // no owner has written anything
+    int bad = -1, code = 0;
+    for (uint32_t j = 0; j < G; ++j) {
+      ShardStep& t = sh[j].st[k];
+      const int rc = rl_set_routed_plan(sh[j].e, t.recv, sh[j].sv_recv, t.n_in, sh[j].pk_reply);
+      t.rc_dec = rc;
+      if (rc && bad < 0) {
+        bad = (int)j;
+        code = rc;
+        t.msg = rl_last_error(sh[j].e);
+      }
+    }
+    for (uint32_t j = 0; j < G; ++j) {
+      ShardStep& t = sh[j].st[k];
+      if (bad >= 0) {
+        if (!t.rc_dec) (void)rl_set_routed_commit(sh[j].e, 0);
+        continue;
+      }
+      const int rc = rl_set_routed_commit(sh[j].e, 1);
+      if (rc) return fail(rc, "%s: shard %u (owner commit): %s", what, j, rl_last_error(sh[j].e));
+    }
+    if (bad >= 0)
+      return fail(code, "%s: shard %d (owner plan): %s: nothing was written anywhere", what, bad,
+                  sh[bad].st[k].msg.c_str());
+  } else {
+    for (uint32_t j = 0; j < G; ++j) {
+      ShardStep& t = sh[j].st[k];
+      const int rc = rl_peek_routed(sh[j].e, t.recv, t.n_in, sh[j].pk_reply, op == OP_FORGET ? (uint32_t)RL_PEEK_ROUTED_FORGET : 0u);
+      if (rc) return fail(rc, "%s: shard %u (owner lookup): %s", what, j, rl_last_error(sh[j].e));
+      he = hipStreamSynchronize(sh[j].v.stream);
+      if (he != hipSuccess) return fail(RL_EHIP, "%s: shard %u (owner lookup): %s", what, j, hipGetErrorString(he));
+    }
   }
   for (uint32_t j = 0; j < G; ++j) {  // owner j's replies, origin-major, into each origin's section j
     uint64_t o = 0;
@@ -1821,12 +1991,18 @@ extern "C" {
 
 int rl_router_peek(rl_router* r, const rl_batch* host_batches, rl_peek_reply* const* out) {
   if (!r || !host_batches || !out) return RL_EINVAL;
-  return r->peek(host_batches, out, false);
+  return r->peek(host_batches, out, OP_PEEK);
 }
 
 int rl_router_forget(rl_router* r, const rl_batch* host_batches, rl_peek_reply* const* out_or_null) {
   if (!r || !host_batches) return RL_EINVAL;
-  return r->peek(host_batches, out_or_null, true);
+  return r->peek(host_batches, out_or_null, OP_FORGET);
+}
+
+int rl_router_set(rl_router* r, const rl_batch* host_batches, const rl_peek_reply* const* values,
+                  rl_peek_reply* const* out_or_null) {
+  if (!r || !host_batches || !values) return RL_EINVAL;
+  return r->peek(host_batches, out_or_null, OP_SET, values);
 }
 
 int rl_router_unique_id(uint8_t* id_out) {

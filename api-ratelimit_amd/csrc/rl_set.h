@@ -41,12 +41,19 @@ struct SetCtl {
   uint32_t pad0[63];
   uint32_t plan[8][64];   // k_set_plan: strings per region that the call would claim a slot for
   uint32_t claim[8][64];  // k_set_apply: slots per region it claimed
+  // k_set_index_routed: per region, over the records that write something, the largest window
+  // generation and the largest complement of one (~smallest; both atomicMax, so zero = none)
+  uint32_t gen_max[8][64];
+  uint32_t gen_minc[8][64];
 };
-static_assert(sizeof(SetCtl) == 17 * 256, "SetCtl layout");
+static_assert(sizeof(SetCtl) == 33 * 256, "SetCtl layout");
 enum : uint32_t {
   SET_ERR_INDEX = 1u,  // the index had no entry left for a string (unreachable: 2^k >= 2 n)
   SET_ERR_MIXED = 2u,  // two identities share one 64-bit sort key in this call: split the call
   SET_ERR_FULL = 4u,   // no free slot in a region (unreachable below the load limit)
+  // the record form only (the host form's host checks refuse these before any launch):
+  SET_ERR_BADREC = 8u,   // a record's rule id is not below n_rules, or its time is above MAX_NOW
+  SET_ERR_BADVAL = 16u,  // a part the record writes: ttl_s / cached_s zero, or its sum with the time not below 2^32
 };
 
 struct SetScratch {
@@ -61,6 +68,13 @@ struct SetScratch {
 // control block are zeroed on the stream by the caller before launch_set_index.
 void launch_set_index(hipStream_t st, const rl_batch& b, const DevRule* rules, uint32_t n_rules, uint64_t seed,
                       const TableDesc& tab, const rl_peek_reply* values, const SetScratch& sc);
+// The record form (rl_set_routed.hip): n routed records (RRec) with one value each beside them.
+void launch_set_index_routed(hipStream_t st, const RRec* recs, const rl_peek_reply* values, uint32_t n,
+                             const DevRule* rules, uint32_t n_rules, const TableDesc& tab, const SetScratch& sc);
+// Origin: vsend[perm[i]] = values[i] for every descriptor the pack gave a record (perm: its strided
+// form, below cap = the records vsend has room for).
+void launch_set_values_pack(hipStream_t st, uint32_t n, uint32_t cap, const uint32_t* perm, const rl_peek_reply* values,
+                            rl_peek_reply* vsend);
 void launch_set_plan(hipStream_t st, uint32_t n_desc, const TableDesc& tab, const SetScratch& sc);
 void launch_set_apply(hipStream_t st, uint32_t n_desc, const TableDesc& tab, const SetScratch& sc);
 

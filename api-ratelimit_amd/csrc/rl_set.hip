@@ -15,6 +15,7 @@
 
 #include "rl_peek.h"
 #include "rl_set.h"
+#include "rl_set_index.h"
 
 namespace rlhip {
 namespace set {
@@ -33,8 +34,7 @@ RL_DEV void count_regions(bool on, uint32_t region, uint32_t (*cnt)[64]) {
 
 // The loads go out as k_peek's do (rl_peek.hip): (offsets, rule id, request index, the value),
 // then (now, the rule entry, the prefix's first 32 bytes), every one unconditional at a clamped
-// index; then the index probe, whose every read is the CAS itself (it returns the word from the
-// L2, never a line this CU cached before another lane's insert).
+// index; then the index probe (rl_set_index.h set_index_tail, shared with k_set_index_routed).
 __global__ __launch_bounds__(NT) void k_set_index(const DevBatch in, const DevRule* __restrict__ rules,
                                                   const uint32_t n_rules, const uint64_t seed, const TableDesc tab,
                                                   const rl_peek_reply* __restrict__ values, const SetScratch sc) {
@@ -67,46 +67,11 @@ __global__ __launch_bounds__(NT) void k_set_index(const DevBatch in, const DevRu
   SetDesc d;
   d.ent = SETD_NONE;
   d.tag = 0u;
-  if (ok && (wc || wf)) {  // the host refused a malformed descriptor before the launch
+  if (ok && (wc || wf)) {  // the host refused a malformed descriptor (and value) before the launch
     const uint32_t t = (uint32_t)now;
     const FpState s = prefix_state_pre(w0, w1, in.blob, o0, len, seed);
     const peek::KeyIdent id = peek::key_ident(s, t, rr);
-    const bool ps = per_second_store(tab, rr.unit);
-    const bool found = (v.flags & RL_PEEK_FOUND) != 0;
-    SetVal sv;
-    sv.count = found ? v.count : 0u;
-    sv.exp = found && !ps ? t + v.ttl_s : 0u;  // below 2^32: host-checked
-    sv.frz = (v.flags & RL_PEEK_LOCAL_CACHED) ? t + v.cached_s : 0u;
-    sv.keeps = (found && (!ps || v.count)) ? SETV_KEEPS : 0u;
-    sc.val[i] = sv;
-
-    const unsigned long long key1 = id.key + 1ull;
-    const uint32_t lg = sc.log2_entries;
-    const uint32_t mask = (1u << lg) - 1u;
-    uint32_t pos = (uint32_t)((key1 * K0) >> (64 - lg));
-    bool placed = false, leader = false;
-    for (uint32_t probe = 0; probe <= mask; ++probe) {
-      const unsigned long long old = atomicCAS(&sc.index[pos].key1, 0ull, key1);
-      if (old == 0ull || old == key1) {
-        placed = true;
-        leader = old == 0ull;
-        break;
-      }
-      pos = (pos + 1u) & mask;
-    }
-    if (!placed) {
-      atomicOr(&sc.ctl->err, SET_ERR_INDEX);
-    } else {
-      SetEntry* e = sc.index + pos;
-      if (leader) {
-        e->tag = (uint32_t)id.lo;
-        e->gen = id.pl.gen;
-      }
-      if (wc) atomicMax(ps ? &e->win_ps : &e->win_main, i + 1u);
-      if (wf) atomicMax(&e->win_cache, i + 1u);
-      d.ent = pos | (leader ? SETD_LEADER : 0u);
-      d.tag = (uint32_t)id.lo;
-    }
+    d = set_index_tail(i, id, t, v, wc, wf, per_second_store(tab, rr.unit), sc);
   }
   sc.desc[i] = d;
 }

@@ -299,6 +299,9 @@ ABI = [
     ("rl_route_unpack_peek", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     ("rl_router_peek", [C.c_void_p, C.POINTER(RlBatch), C.POINTER(C.c_void_p)], C.c_int),
     ("rl_router_forget", [C.c_void_p, C.POINTER(RlBatch), C.POINTER(C.c_void_p)], C.c_int),
+    ("rl_set_routed_plan", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p], C.c_int),
+    ("rl_set_routed_commit", [C.c_void_p, C.c_int], C.c_int),
+    ("rl_router_set", [C.c_void_p, C.POINTER(RlBatch), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)], C.c_int),
     ("rl_resize", [C.c_void_p, C.POINTER(C.c_uint32)], C.c_int),
     ("rl_rule_stats_add_device", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
     ("rl_rule_stats_read", [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32], C.c_int),
@@ -809,6 +812,19 @@ class Engine:
         self._check(self.lib.rl_peek_routed(self.h, rec_ptr or None, n, reply_ptr or None,
                                             PEEK_ROUTED_FORGET if forget else 0), "rl_peek_routed")
 
+    def set_routed_plan(self, rec_ptr: int, val_ptr: int, n: int, reply_ptr: int = 0):
+        """rl_set_routed_plan: phase 1 of a routed set over n routed records (ROUTE_RECORD_BYTES each)
+        and their n values (PEEK_DTYPE) in device memory: the replies (the state before the call) to
+        reply_ptr when it is not 0, then the index and the plan. Synchronous; on return a plan is
+        open and nothing has been written, or RedisError and no plan is open."""
+        self._check(self.lib.rl_set_routed_plan(self.h, rec_ptr or None, val_ptr or None, n, reply_ptr or None),
+                    "rl_set_routed_plan")
+
+    def set_routed_commit(self, apply: bool = True):
+        """rl_set_routed_commit: phase 2. apply: write the plan and publish the occupancy as rl_set
+        does; else drop it."""
+        self._check(self.lib.rl_set_routed_commit(self.h, int(bool(apply))), "rl_set_routed_commit")
+
     def route_unpack_peek(self, n_desc: int, perm_ptr: int, back_ptr: int, out_ptr: int):
         """rl_route_unpack_peek: out[i] = back[perm[i]] (NIL where perm[i] is ROUTE_LOCAL), all in
         device memory, asynchronous on the engine stream."""
@@ -1176,6 +1192,26 @@ class Router:
         """rl_router_forget: the same call, clearing at each owner after every lookup of the call;
         returns the replies as read before the clears."""
         return self._peek(batches, self.lib.rl_router_forget, "rl_router_forget")
+
+    def set(self, batches, values, want_out: bool = True):
+        """rl_router_set: per engine passed at create a host Batch and its values (PEEK_DTYPE, one per
+        descriptor: Engine.set's), each descriptor written at the owner of its key, all owners or
+        none. Collective like peek / forget (an empty Batch where a rank sets nothing). Returns one
+        PEEK_DTYPE array per batch, the state before the call, or None."""
+        vals = [np.ascontiguousarray(v, PEEK_DTYPE) for v in values]
+        for b, v in zip(batches, vals):
+            if v.shape != (b.n_desc,):
+                raise ValueError(f"rl_router_set: {v.shape} values for {b.n_desc} descriptors")
+        structs = [_batch_struct(b) for b in batches]
+        for s in structs:  # (ignored by the call; staged as zeros)
+            s.hits_addend, s.ttl_jitter = None, None
+        arr = (RlBatch * self.n)(*structs)
+        pads = [v if v.shape[0] else np.zeros(1, PEEK_DTYPE) for v in vals]
+        va = (C.c_void_p * self.n)(*[x.ctypes.data for x in pads])
+        outs = [np.zeros(max(1, b.n_desc), PEEK_DTYPE) for b in batches]
+        o = (C.c_void_p * self.n)(*[x.ctypes.data for x in outs]) if want_out else None
+        self._check(self.lib.rl_router_set(self.h, arr, va, o), "rl_router_set")
+        return [outs[i][:b.n_desc] for i, b in enumerate(batches)] if want_out else None
 
     def allgather_host(self, data: bytes, n_ranks: int) -> list:
         """rl_router_allgather_host: every rank's `data` (the same length everywhere), in rank

@@ -779,8 +779,8 @@ int rl_forget(rl_engine* e, const rl_batch* host_batch, rl_peek_reply* out_or_nu
  * is to be reset or restored, as after any failed stream.
  * The index (32 B x the power of two >= 2 x max_batch_desc) and two per-descriptor scratch arrays
  * (40 B x max_batch_desc) are allocated at the first call and kept.
- * Out of scope: a routed rl_router_set (the routed forget's pack and exchanges would carry it;
- * until then a rank can rl_set the keys it owns), a device-memory public form, a compact wire form. */
+ * Behind a router the call is rl_router_set ("Routed set" below).
+ * Out of scope: a device-memory public form, a compact wire form. */
 enum { RL_SET_KEEP_COUNTER = 32u, RL_SET_KEEP_CACHE = 64u }; /* rl_peek_reply.flags, input only */
 int rl_set(rl_engine* e, const rl_batch* host_batch, const rl_peek_reply* values, rl_peek_reply* out_or_null);
 
@@ -832,6 +832,71 @@ int rl_route_unpack_peek(rl_engine* e, const rl_batch* device_batch, const uint3
                          const rl_peek_reply* d_back, rl_peek_reply* d_out);
 int rl_router_peek(rl_router* r, const rl_batch* host_batches, rl_peek_reply* const* out);
 int rl_router_forget(rl_router* r, const rl_batch* host_batches, rl_peek_reply* const* out_or_null);
+
+/* ---- Routed set --------------------------------------------------------------
+ * rl_set where the keys are spread over the shards of a router: the cutover of a multi-GPU
+ * deployment from Redis (every rank imports whatever share of the SCAN it likes) and the move of
+ * counters to a router of another size ("peek there, set here"; a snapshot needs the same
+ * n_shards). A routed set can claim table slots and can be refused at an owner after the records
+ * have moved (RL_ENOSPC, a window generation that is over, two identities on one sort key), so it is
+ * two-phase: every owner plans, the plan statuses are exchanged, and only if all are zero does any
+ * owner write.
+ *
+ * Engine level (device memory, between batches):
+ * rl_set_routed_plan: phase 1 over n routed records (RL_ROUTE_RECORD_BYTES each, as
+ * rl_route_pack_strided writes them) with one value each beside them (d_values[i] for record i,
+ * rl_set's value semantics). Replies (the state before the call, rl_peek_routed's) go to d_reply
+ * when it is not NULL; then the records are indexed and planned exactly as rl_set's descriptors are.
+ * Record order is the serial order: the last record of a string that writes a part wins it. The
+ * call synchronises the engine stream. 0: a plan is open and nothing has been written. Any other
+ * return: nothing written and no plan open:
+ *   RL_ESTATE     a batch in flight, a restore open, or a plan already open
+ *   RL_ECAPACITY  n above max_batch_desc, or max_batch_desc above 2^29
+ *   RL_EINVAL     null arrays with n > 0; a record whose rule id is not below the loaded rule
+ *                 count or whose time is above 0xFFFD0000; of the parts a record writes: a FOUND
+ *                 main-store value with ttl_s == 0, a LOCAL_CACHED value with cached_s == 0, a sum
+ *                 with the time not below 2^32; two window generations of one region among the
+ *                 records that write something; a generation that is over (rl_set's rule). All of
+ *                 these are found on the device: the owner's host never sees records or values
+ *   RL_EDEVICE    two identities share one 64-bit sort key, or the index overflowed
+ *   RL_ENOSPC     rl_set's check: a region's live slots plus the plan's claims pass its load limit
+ *   RL_EHIP
+ * n == 0 opens an empty plan whose commit does nothing (a rank that receives nothing keeps the
+ * collective sequence). While a plan is open every entry point that an open restore refuses
+ * returns RL_ESTATE; rl_reset and rl_destroy close the plan.
+ * rl_set_routed_commit: phase 2. apply != 0 runs rl_set's applying pass and publishes the occupancy
+ * exactly as rl_set does (and fails as it does); apply == 0 drops the plan. RL_ESTATE with no plan
+ * open. Either way the plan is closed.
+ *
+ * rl_router_set: rl_router_forget's contract. Collective; one batch, one value array and one output
+ * (or NULL) per engine passed at create; host memory, synchronous; a rank with nothing to set passes
+ * n_desc == 0; RL_ESTATE before any collective while a step is in flight.
+ *   1. Origin: rl_router_peek's refusals plus rl_set's per-value checks; the batch and the values are
+ *      staged, packed by owner (one record per descriptor) and the values laid out like the records.
+ *      A refusal here travels as this origin's status in the counts exchange: nothing is planned
+ *      anywhere, the failing rank returns its code (local transport: the first failing shard's) and
+ *      the others RL_EPEER.
+ *   2. Counts, then records and values in one collective group.
+ *   3. Every owner runs rl_set_routed_plan over everything it received, origin-major: "the last SET
+ *      wins" is taken with the origins' batches one after another in shard order, descriptor order
+ *      inside each, per part.
+ *   4. Each owner's plan code goes to every rank. If any is non-zero every owner drops its plan:
+ *      the failing rank returns its code and the others RL_EPEER (local transport: the first failing
+ *      shard's code). No owner has written anything and out is untouched.
+ *   5. Every owner commits; the replies (the state before the call, for every duplicate across
+ *      descriptors and origins) and the commit status return by the reverse exchange and the origin
+ *      unpacks them into out. A HIP or communicator failure in this phase leaves per-owner
+ *      atomicity, as rl_set's applying pass and a routed forget document.
+ * The call does not move the step clock, cannot return RL_ELATE, does not touch the hot sets and
+ * leaves rl_router_stats alone. Its value staging and two value buffers are allocated at the first
+ * call, beside the routed peek's buffers. An engine's max_batch_desc bounds what one owner can
+ * receive in one call (RL_ECAPACITY from its plan).
+ * Out of scope: a set while steps are in flight, a device-memory form of the router call. */
+int rl_set_routed_plan(rl_engine* e, const void* d_records, const rl_peek_reply* d_values, uint32_t n,
+                       rl_peek_reply* d_reply_or_null);
+int rl_set_routed_commit(rl_engine* e, int apply);
+int rl_router_set(rl_router* r, const rl_batch* host_batches, const rl_peek_reply* const* values,
+                  rl_peek_reply* const* out_or_null);
 
 /* ---- Rule stats: per-rule stat counters summed on the device ---------------
  * The reference keeps four counters per limit, <FullKey>.total_hits / .over_limit / .near_limit /
