@@ -286,6 +286,57 @@ void HipRateLimitCache::Resize(const uint32_t log2_slots[4]) {
   control([this, lg]() -> std::string { return rl_resize(eng_, lg) ? rl_last_error(eng_) : ""; });
 }
 
+// Merge: the file is read here, on the caller's thread; every chunk is a control call of its own,
+// so what was enqueued while a chunk ran is decided before the next one.
+HipRateLimitCache::MergeReport HipRateLimitCache::Merge(const std::string& path, uint64_t first_record) {
+  File fp{fopen(path.c_str(), "rb")};
+  if (!fp.f) throw RedisError("hip backend: Merge: cannot open " + path);
+  rl_snapshot_header h;
+  if (fread(&h, sizeof h, 1, fp.f) != 1)
+    throw RedisError("hip backend: Merge: " + path + " is shorter than a snapshot header");
+  if (fseek(fp.f, 0, SEEK_END)) throw RedisError("hip backend: Merge: cannot seek " + path);
+  const long size = ftell(fp.f);
+  const uint64_t body = size < (long)sizeof h ? ~0ull : (uint64_t)size - sizeof h;
+  if (h.record_bytes != RL_SNAP_RECORD_BYTES || body % RL_SNAP_RECORD_BYTES ||
+      body / RL_SNAP_RECORD_BYTES != h.n_records)
+    throw RedisError("hip backend: Merge: " + path + " does not hold the header and its n_records records");
+  if (first_record > h.n_records)
+    throw RedisError("hip backend: Merge: first_record is past the file's n_records");
+  if (fseek(fp.f, (long)(sizeof h + first_record * RL_SNAP_RECORD_BYTES), SEEK_SET))
+    throw RedisError("hip backend: Merge: cannot seek " + path);
+  const uint32_t chunk = std::max(1u, std::min(kSnapChunk, s_.batch_limit));
+  std::vector<uint8_t> buf((size_t)chunk * RL_SNAP_RECORD_BYTES);
+  MergeReport total;
+  uint64_t done = first_record;
+  // (a file without records left still has its header checked by the engine: one empty call)
+  for (bool first = true; first || done < h.n_records; first = false) {
+    const uint32_t n = (uint32_t)std::min<uint64_t>(h.n_records - done, chunk);
+    if (n && fread(buf.data(), RL_SNAP_RECORD_BYTES, n, fp.f) != n)
+      throw MergeError("hip backend: Merge: read failed: " + path + " (" + std::to_string(done) + " records merged)", done);
+    rl_merge_report rep;
+    memset(&rep, 0, sizeof rep);
+    try {
+      control([this, &h, &buf, n, &rep]() -> std::string {
+        if (trace_) trace_(nullptr, staged_seq_, kTraceControl);
+        if (rl_merge(eng_, &h, buf.data(), n, ts_->UnixNow(), &rep)) return rl_last_error(eng_);
+        grow_after_ctl_ = true;  // the chunk may have claimed slots: the watermark check of a completed batch
+        return "";
+      });
+    } catch (const RedisError& e) {
+      throw MergeError(std::string(e.what()) + " (Merge: " + std::to_string(done) + " records of " + path +
+                           " are merged; after a Resize resume with first_record = " + std::to_string(done) + ")",
+                       done);
+    }
+    total.Records += rep.records;
+    total.Folded += rep.folded;
+    total.Claimed += rep.claimed;
+    total.DroppedOver += rep.dropped_over;
+    total.DroppedEmpty += rep.dropped_empty;
+    done += n;
+  }
+  return total;
+}
+
 rl_occupancy HipRateLimitCache::Occupancy() {
   rl_occupancy o;
   memset(&o, 0, sizeof o);

@@ -278,6 +278,30 @@ class HipRateLimitCache : public RateLimitCache {
   void Resize(const uint32_t log2_slots[4]);
   rl_occupancy Occupancy();
 
+  // Merge (rl_hip.h "Merge"): a snapshot file's records, from record first_record on, folded into
+  // the live counters while the cache serves: counters add, expiries and local-cache deadlines
+  // take the later one, absent strings are claimed. The file is read on the caller's thread and
+  // every chunk (at most min(2^16, batch_limit) records) is ONE control call of its own, so the
+  // DoLimit calls enqueued meanwhile are decided between two chunks, not behind the whole file:
+  // callers are held for one chunk's rl_merge at a time. Each chunk's time is ts_->UnixNow()
+  // taken on the submitter thread, each is reported to the trace hook as (the next batch to be
+  // gathered, kTraceControl) with a null request, and after each the auto-grow check runs as after
+  // a Set (a chunk can claim slots). A chunk the engine refuses throws RedisError naming how many
+  // records of the file are merged (those stay merged; the refused chunk changed nothing), so
+  // after a Resize the caller resumes with first_record = that number; MergeError carries it.
+  // A malformed file throws before anything is merged. The same chunk merged twice adds twice.
+  // HIP_LOCAL_CACHE=freecache: the host cache is neither read nor written. Needs the writer's
+  // HIP_HASH_SEED and REDIS_PERSECOND; the table sizes may differ. HipRoutedRateLimitCache has no
+  // Merge (records carry no owner): consolidate into one engine, or let a rank take back its own.
+  struct MergeReport {
+    uint64_t Records = 0, Folded = 0, Claimed = 0, DroppedOver = 0, DroppedEmpty = 0;
+  };
+  struct MergeError : RedisError {
+    MergeError(const std::string& msg, uint64_t merged) : RedisError(msg), Merged(merged) {}
+    uint64_t Merged;  // records of the file merged before the refusal (first_record included)
+  };
+  MergeReport Merge(const std::string& path, uint64_t first_record = 0);
+
   // Batcher counters (tests): batches submitted, rule-table loads, and loads made while an
   // earlier batch was still in flight (append-only rule table, rl_hip.h rl_load_rules).
   // drains: times the batches in flight were completed early so that a rule-table load or a

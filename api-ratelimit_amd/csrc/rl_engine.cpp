@@ -23,6 +23,7 @@
 #include "rl_common.h"
 #include "rl_hip.h"
 #include "rl_internal.h"
+#include "rl_merge.h"
 #include "rl_resolve.h"
 #include "rl_set.h"
 #include "rl_snapshot.h"
@@ -94,13 +95,14 @@ namespace {
 enum KernelId {
   KT_FINGERPRINT, KT_HISTOGRAM, KT_HIST_SCAN, KT_SORT_PASS, KT_SCAN, KT_LEADER, KT_DECIDE, KT_FALLBACK, KT_MEMSET,
   KT_CAND, KT_V4_HIST, KT_V4_SCAN, KT_V4_PLACE, KT_V4_GROUP, KT_RESOLVE, KT_RULE_STATS, KT_CACHE_STATS, KT_CENSUS,
-  KT_SET_INDEX, KT_SET_PLAN, KT_SET_APPLY, KT_SET_INDEX_ROUTED, KT_COUNT
+  KT_SET_INDEX, KT_SET_PLAN, KT_SET_APPLY, KT_SET_INDEX_ROUTED, KT_MERGE_PLAN, KT_MERGE_APPLY, KT_COUNT
 };
 const char* const kKernelNames[KT_COUNT] = {"k_fingerprint", "k_histogram", "k_hist_scan", "k_sort_pass", "k_scan",
                                             "k_leader",      "k_decide",    "fallback",    "memset",      "k_cand_state",
                                             "k4_hist",       "k4_scan",     "k4_place",    "k4_group",
                                             "k_resolve",     "k_rule_stats", "k_cache_stats", "k_census",
-                                            "k_set_index",   "k_set_plan",  "k_set_apply", "k_set_index_routed"};
+                                            "k_set_index",   "k_set_plan",  "k_set_apply", "k_set_index_routed",
+                                            "k_merge_plan",  "k_merge_apply"};
 
 enum Mode { MODE_LSD = 1, MODE_LSD_FULL = 2, MODE_V4 = 4 };
 
@@ -179,6 +181,13 @@ struct rl_engine {
   int set_busy(const char* what) {
     return set_open ? fail(RL_ESTATE, "%s while a routed set plan is open (call rl_set_routed_commit)", what) : 0;
   }
+  // rl_merge's own scratch beside rl_set's index (rl_merge.h): the call's records on the device
+  // (max_batch_desc of them) and the control block with its pinned copy, allocated at the first
+  // call and kept
+  Slot* d_merge_recs = nullptr;
+  MergeCtl* d_merge_ctl = nullptr;
+  MergeCtl* h_merge_ctl = nullptr;
+  int merge_ensure();
   // what is folded in behind a batch: COUNT_RULE (k_rule_stats) | COUNT_CACHE (k_cache_stats)
   enum : uint32_t { COUNT_RULE = 1u, COUNT_CACHE = 2u };
   int count_batch(const rl_batch& b, const rl_status* out, const EngineCtl* ctl, uint32_t which);
@@ -1305,7 +1314,7 @@ void rl_destroy(rl_engine* e) {
   for (void* p : {(void*)e->v4_hoff, (void*)e->v4_dfr, (void*)e->v4_hb,
                   e->v4_scratch, (void*)e->d_poison, (void*)e->d_tree_nodes,
                   (void*)e->d_tree_slots, (void*)e->d_tree_names, (void*)e->d_tree_fnodes, (void*)e->d_tree_fslots, (void*)e->d_res, (void*)e->d_res_flags, (void*)e->table, (void*)e->d_occ,
-                  (void*)e->d_rules, (void*)e->d_rstats, (void*)e->d_cstats, (void*)e->d_census, (void*)e->set_sc.index, (void*)e->set_sc.val, (void*)e->set_sc.desc, (void*)e->set_sc.ctl, (void*)e->d_set_vals, (void*)e->keys_orig, (void*)e->keys_a, (void*)e->keys_b, (void*)e->vals_a,
+                  (void*)e->d_rules, (void*)e->d_rstats, (void*)e->d_cstats, (void*)e->d_census, (void*)e->set_sc.index, (void*)e->set_sc.val, (void*)e->set_sc.desc, (void*)e->set_sc.ctl, (void*)e->d_set_vals, (void*)e->d_merge_recs, (void*)e->d_merge_ctl, (void*)e->keys_orig, (void*)e->keys_a, (void*)e->keys_b, (void*)e->vals_a,
                   (void*)e->vals_b, (void*)e->recs, (void*)e->srec, (void*)e->seg, (void*)e->offs,
                   (void*)e->hist_part, (void*)e->fp_part, (void*)e->fp_part2, (void*)e->tile_heads,
                   (void*)e->zero_block, (void*)e->d_cand, (void*)e->r_tmp, (void*)e->r_own, (void*)e->r_bcnt,
@@ -1315,6 +1324,7 @@ void rl_destroy(rl_engine* e) {
   hipHostFree(e->h_route);
   hipHostFree(e->h_census);
   hipHostFree(e->h_set_ctl);
+  hipHostFree(e->h_merge_ctl);
   for (hipStream_t s : {e->front, e->xin, e->xout, e->own_stream})
     if (s) hipStreamDestroy(s);
   delete e;
@@ -2021,11 +2031,9 @@ int rl_snapshot_end(rl_engine* e) {
   return 0;
 }
 
-int rl_restore_begin(rl_engine* e, const rl_snapshot_header* h) {
-  if (!e || !h) return RL_EINVAL;
-  if (e->n_fl) return e->fail(RL_ESTATE, "rl_restore_begin while a batch is in flight (call rl_wait)");
-  if (e->restoring) return e->fail(RL_ESTATE, "a restore is open (call rl_restore_end)");
-  if (int rc = e->set_busy("rl_restore_begin")) return rc;
+// What a header must say before its records are taken (rl_restore_begin, rl_merge): the format,
+// the reserved words, the seed, and of the settings those in `need` (differ: RL_EINVAL with `differs`).
+static int snap_header_check(rl_engine* e, const rl_snapshot_header* h, uint32_t need, const char* differs) {
   if (memcmp(h->magic, kSnapMagic, 8)) return e->fail(RL_EINVAL, "snapshot header: bad magic");
   if (h->header_bytes != RL_SNAP_HEADER_BYTES || h->record_bytes != RL_SNAP_RECORD_BYTES)
     return e->fail(RL_EINVAL, "snapshot header: header / record size %u / %u, expected %u / %u", h->header_bytes,
@@ -2036,9 +2044,18 @@ int rl_restore_begin(rl_engine* e, const rl_snapshot_header* h) {
     if (w) return e->fail(RL_EINVAL, "snapshot header: a reserved word is set");
   if (h->seed_check != snap_seed_check(e->cfg.hash_seed))
     return e->fail(RL_EINVAL, "snapshot taken under another hash_seed");
-  const uint32_t need = RL_SNAP_SPLIT | RL_SNAP_LAG;
-  if ((h->flags & need) != (snap_flags(e) & need))
-    return e->fail(RL_EINVAL, "snapshot per_second_split / lag window setting differs from this engine's");
+  if ((h->flags & need) != (snap_flags(e) & need)) return e->fail(RL_EINVAL, "%s", differs);
+  return 0;
+}
+
+int rl_restore_begin(rl_engine* e, const rl_snapshot_header* h) {
+  if (!e || !h) return RL_EINVAL;
+  if (e->n_fl) return e->fail(RL_ESTATE, "rl_restore_begin while a batch is in flight (call rl_wait)");
+  if (e->restoring) return e->fail(RL_ESTATE, "a restore is open (call rl_restore_end)");
+  if (int rc = e->set_busy("rl_restore_begin")) return rc;
+  if (int rc = snap_header_check(e, h, RL_SNAP_SPLIT | RL_SNAP_LAG,
+                                 "snapshot per_second_split / lag window setting differs from this engine's"))
+    return rc;
   uint64_t total = 0;
   for (int r = 0; r < 8; ++r) {
     const bool lazy = lazy_region(e->tab.lag, (uint32_t)r);
@@ -2131,6 +2148,164 @@ int rl_restore_end(rl_engine* e) {
   he = hipMemcpy(e->d_occ, e->occ, sizeof e->occ, hipMemcpyHostToDevice);
   if (he != hipSuccess) return e->hip_fail(he, "rl_restore_end: publish occupancy");
   e->st.live_keys = e->live_total();
+  return 0;
+}
+
+// ---- Merge --------------------------------------------------------------------------------
+// A call's claims into the mirror and onto the device as rl_resize publishes the occupancy
+// (rl_set's applying pass and rl_merge's end alike); nothing changes with no claim.
+static int publish_claims(rl_engine* e, const char* what, const RegionOcc nocc[8], uint64_t claims) {
+  if (!claims) return 0;
+  const hipError_t he = hipMemcpy(e->d_occ, nocc, 8 * sizeof(RegionOcc), hipMemcpyHostToDevice);
+  if (he != hipSuccess) return e->hip_fail(he, (std::string(what) + ": publish occupancy").c_str());
+  memcpy(e->occ, nocc, 8 * sizeof(RegionOcc));
+  e->st.inserted_keys += claims;
+  e->st.live_keys = e->live_total();
+  return 0;
+}
+
+int rl_engine::merge_ensure() {
+  if (d_merge_recs) return 0;
+  const uint64_t n = cfg.max_batch_desc ? cfg.max_batch_desc : 1u;
+  Slot* recs_buf = nullptr;
+  MergeCtl *dc = nullptr, *hc = nullptr;
+  hipError_t he = hipMalloc(&recs_buf, n * sizeof(Slot));
+  if (he == hipSuccess) he = hipMalloc(&dc, sizeof(MergeCtl));
+  if (he == hipSuccess) he = hipHostMalloc(&hc, sizeof(MergeCtl), hipHostMallocDefault);
+  if (he != hipSuccess) {
+    (void)hipGetLastError();
+    hipFree(recs_buf);
+    hipFree(dc);
+    return hip_fail(he, "rl_merge scratch allocation");
+  }
+  d_merge_recs = recs_buf;
+  d_merge_ctl = dc;
+  h_merge_ctl = hc;
+  return 0;
+}
+
+// rl_merge: every check first (host: the call's place, the header, every record, the target
+// generations; device: one identity per index entry, the exact claims per region against the load
+// limits), then the applying pass, then the occupancy as rl_set's applying pass publishes it.
+int rl_merge(rl_engine* e, const rl_snapshot_header* h, const void* host_recs, uint32_t n, int64_t now,
+             rl_merge_report* report) {
+  if (!e || !h) return RL_EINVAL;
+  if (e->n_fl) return e->fail(RL_ESTATE, "rl_merge while a batch is in flight (call rl_wait)");
+  if (e->restoring) return e->fail(RL_ESTATE, "rl_merge between rl_restore_begin and rl_restore_end");
+  if (int rc = e->set_busy("rl_merge")) return rc;
+  if (e->cfg.max_batch_desc > SET_MAX_DESC)
+    return e->fail(RL_ECAPACITY, "rl_merge: max_batch_desc %u above 2^29", e->cfg.max_batch_desc);
+  if (n > e->cfg.max_batch_desc)
+    return e->fail(RL_ECAPACITY, "rl_merge: %u records exceed max_batch_desc %u", n, e->cfg.max_batch_desc);
+  if (int rc = snap_header_check(e, h, RL_SNAP_SPLIT, "snapshot per_second_split setting differs from this engine's"))
+    return rc;
+  if (now < 0 || now > MAX_NOW) return e->fail(RL_EINVAL, "rl_merge: now outside [0, 0xFFFD0000]");
+  if (n && !host_recs) return e->fail(RL_EINVAL, "rl_merge: null record buffer");
+  const Slot* src = static_cast<const Slot*>(host_recs);
+  const uint32_t t = (uint32_t)now;
+  const bool lc = e->tab.local_cache != 0;
+  SnapGens T;
+  for (int r = 0; r < 8; ++r) T.gen[r] = e->occ[r].gen;  // nothing is in flight: the mirror's are the table's
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t g = (uint32_t)src[i].ctrl, r = key_region(src[i].key);
+    if (!g) return e->fail(RL_EINVAL, "rl_merge: record %u: window generation 0", i);
+    const uint64_t ws = (uint64_t)(g - 1u) * unit_div(r / 2u + 1u);
+    const Place pl = ws <= (uint64_t)MAX_NOW ? place_of((uint32_t)ws) : Place{8u, 0u};
+    if (pl.region != r || pl.gen != g)
+      return e->fail(RL_EINVAL, "rl_merge: record %u: no engine writes window generation %u in table region %u", i, g, r);
+    if (g > T.gen[r] && merge_leaves(MergeState{src[i].count, src[i].exp, src[i].pcount, src[i].frz}, t, lc))
+      T.gen[r] = g;
+  }
+  rl_merge_report rep;
+  memset(&rep, 0, sizeof rep);
+  rep.records = n;
+  if (!n) {
+    if (report) *report = rep;
+    return 0;
+  }
+  int rc = e->set_ensure();
+  if (!rc) rc = e->merge_ensure();
+  if (!rc) rc = e->snap_alloc();
+  if (rc) return rc;
+  // stage through the restore's pinned buffer: it is reused once the previous piece's copy has left it
+  hipError_t he = hipSuccess;
+  for (uint32_t done = 0; done < n && he == hipSuccess;) {
+    const uint32_t m = std::min(n - done, rl_engine::SNAP_STAGE_RECS);
+    he = hipEventSynchronize(e->ev_snap);
+    if (he == hipSuccess) {
+      memcpy(e->h_snap_stage, src + done, (size_t)m * sizeof(Slot));
+      he = hipMemcpyAsync(e->d_merge_recs + done, e->h_snap_stage, (size_t)m * sizeof(Slot), hipMemcpyHostToDevice,
+                          e->stream);
+    }
+    if (he == hipSuccess) he = hipEventRecord(e->ev_snap, e->stream);
+    done += m;
+  }
+  MergeArgs a;
+  a.recs = e->d_merge_recs;
+  a.n = n;
+  a.now = t;
+  a.T = T;
+  a.index = e->set_sc.index;
+  a.log2_entries = 6;
+  while ((1ull << a.log2_entries) < 2ull * n) ++a.log2_entries;  // <= the allocation's: n <= max_batch_desc
+  a.desc = e->set_sc.desc;
+  a.ctl = e->d_merge_ctl;
+  MergeCtl* hc = e->h_merge_ctl;
+  if (he == hipSuccess) he = hipMemsetAsync(a.index, 0, sizeof(SetEntry) << a.log2_entries, e->stream);
+  if (he == hipSuccess) he = hipMemsetAsync(a.ctl, 0, sizeof(MergeCtl), e->stream);
+  if (he == hipSuccess) {
+    e->timed(KT_MERGE_PLAN, [&] { launch_merge_plan(e->stream, e->tab, a); });
+    he = hipGetLastError();
+  }
+  if (he == hipSuccess) he = hipMemcpyAsync(hc, a.ctl, sizeof(MergeCtl), hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  if (he != hipSuccess) return e->hip_fail(he, "rl_merge (nothing written)");
+  if (e->timing) e->fold_marks();
+  if (hc->err & MERGE_ERR_DUP)
+    return e->fail(RL_EINVAL, "rl_merge: one identity (claim word, key) occurs twice in the call (nothing written)");
+  if (hc->err & MERGE_ERR_MIXED)
+    return e->fail(RL_EDEVICE, "rl_merge: two identities of the call share one 64-bit sort key: split the call "
+                               "(nothing written)");
+  if (hc->err) return e->fail(RL_EDEVICE, "rl_merge: the call's index overflowed (nothing written)");
+  uint32_t planned[8];
+  for (int r = 0; r < 8; ++r) {
+    const uint32_t c = planned[r] = hc->plan[2 * r][0] + hc->plan[2 * r + 1][0];
+    if (!c) continue;
+    const uint64_t live = region_live(e->occ[r], lazy_region(e->tab.lag, (uint32_t)r), T.gen[r]);
+    if (live + c > e->occ[r].limit)
+      return e->fail(RL_ENOSPC, "rl_merge: table region %d holds %llu live slots and the call claims %u, over its load "
+                                "limit of %u (nothing written)", r, (unsigned long long)live, c, e->occ[r].limit);
+  }
+  rep.dropped_over = hc->over[0];
+  rep.dropped_empty = hc->empty[0];
+  e->timed(KT_MERGE_APPLY, [&] { launch_merge_apply(e->stream, e->tab, a); });
+  he = hipGetLastError();
+  if (he == hipSuccess) he = hipMemcpyAsync(hc, a.ctl, sizeof(MergeCtl), hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  if (he != hipSuccess) return e->hip_fail(he, "rl_merge: applying pass (the table may hold part of the call)");
+  if (e->timing) e->fold_marks();
+  if (hc->err)
+    return e->fail(RL_EDEVICE, "rl_merge: a region had no free slot left (the table may hold part of the call)");
+  RegionOcc nocc[8];
+  uint64_t claims = 0;
+  for (int r = 0; r < 8; ++r) {
+    nocc[r] = e->occ[r];
+    const bool lazy = lazy_region(e->tab.lag, (uint32_t)r);
+    const uint32_t cn = hc->claim[2 * r][0], cp = hc->claim[2 * r + 1][0];
+    if (cn + cp != planned[r])
+      return e->fail(RL_EDEVICE, "rl_merge: region %d claimed %u slots where the plan counted %u (the table may hold "
+                                 "part of the call)", r, cn + cp, planned[r]);
+    // the newest class first: a target generation above the region's comes with a claim of it
+    // (nothing of it is in the table), so the previous class always lands behind occ.gen == T
+    if (cn) occ_advance(nocc[r], lazy, T.gen[r], cn);
+    if (cp) occ_advance(nocc[r], lazy, T.gen[r] - 2u, cp);
+    claims += (uint64_t)cn + cp;
+  }
+  rc = publish_claims(e, "rl_merge", nocc, claims);
+  if (rc) return rc;
+  rep.claimed = claims;
+  rep.folded = hc->folded[0];
+  if (report) *report = rep;
   return 0;
 }
 
@@ -2437,14 +2612,7 @@ static int set_apply(rl_engine* e, const char* what, uint32_t n, const SetScratc
     if (c) occ_advance(nocc[r], lazy_region(e->tab.lag, (uint32_t)r), gcall[r], c);
     claims += c;
   }
-  if (claims) {
-    he = hipMemcpy(e->d_occ, nocc, sizeof nocc, hipMemcpyHostToDevice);
-    if (he != hipSuccess) return e->hip_fail(he, (std::string(what) + ": publish occupancy").c_str());
-    memcpy(e->occ, nocc, sizeof nocc);
-    e->st.inserted_keys += claims;
-    e->st.live_keys = e->live_total();
-  }
-  return 0;
+  return publish_claims(e, what, nocc, claims);
 }
 
 // rl_set: every check first (host: shape, values, window generations; device: one identity per

@@ -162,6 +162,13 @@ class RlSnapshotHeader(C.Structure):
                 ("src_log2", C.c_uint32 * 8), ("reserved", C.c_uint32 * 22)]
 
 
+MERGE_REPORT_FIELDS = ("records", "folded", "claimed", "dropped_over", "dropped_empty")
+
+
+class RlMergeReport(C.Structure):  # rl_merge_report, 64 B
+    _fields_ = [(f, C.c_uint64) for f in MERGE_REPORT_FIELDS] + [("reserved", C.c_uint64 * 3)]
+
+
 def _check_snapshot_header(h: "RlSnapshotHeader"):
     if bytes(h.magic) != SNAP_MAGIC:
         raise ValueError("snapshot: bad magic")
@@ -291,6 +298,8 @@ ABI = [
     ("rl_restore_begin", [C.c_void_p, C.POINTER(RlSnapshotHeader)], C.c_int),
     ("rl_restore_put", [C.c_void_p, C.c_void_p, C.c_uint32], C.c_int),
     ("rl_restore_end", [C.c_void_p], C.c_int),
+    ("rl_merge", [C.c_void_p, C.POINTER(RlSnapshotHeader), C.c_void_p, C.c_uint32, C.c_int64,
+                  C.POINTER(RlMergeReport)], C.c_int),
     ("rl_peek", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
     ("rl_peek_device", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
     ("rl_forget", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
@@ -348,6 +357,16 @@ class RedisError(RuntimeError):
     def __init__(self, msg: str, code: Optional[int] = None):
         super().__init__(msg)
         self.code = code
+
+
+class MergeRefused(RedisError):
+    """Engine.merge_records / merge: a chunk was refused. `merged` records (the chunks before it)
+    are in the table and stay there, `report` is their summed report, `code` the RL_E* code; after
+    a resize the caller resumes from record `merged`."""
+
+    def __init__(self, msg: str, code, merged: int, report: dict):
+        super().__init__(f"{msg} ({merged} records merged before it)", code)
+        self.merged, self.report = merged, report
 
 
 # ---------------------------------------------------------------------------
@@ -979,6 +998,69 @@ class Engine:
             self.restore_end()
         return h
 
+    # ---- merge (rl_hip.h "Merge") ----
+    def merge_chunk(self, header: RlSnapshotHeader, records: np.ndarray, now: int) -> dict:
+        """rl_merge: one chunk of a snapshot's records (SNAP_DTYPE, at most max_batch_desc) folded
+        into the live table at time `now`, between batches. Returns the call's report. RedisError
+        as the engine refuses; a refusal changes nothing."""
+        records = np.ascontiguousarray(records)
+        if records.dtype.itemsize != SNAP_RECORD_BYTES or records.ndim != 1:
+            raise ValueError("snapshot records are a 1-D array of 32-byte items")
+        rep = RlMergeReport()
+        self._check(self.lib.rl_merge(self.h, C.byref(header), _ptr(records) or None, records.shape[0], now,
+                                      C.byref(rep)), "rl_merge")
+        return {f: int(getattr(rep, f)) for f in MERGE_REPORT_FIELDS}
+
+    def merge_records(self, header: RlSnapshotHeader, records: np.ndarray, now: int, chunk: Optional[int] = None) -> dict:
+        """Merge a record set in chunks of `chunk` (default min(SNAP_CHUNK, max_batch_desc)): the
+        summed reports. Batches may be submitted between two calls of merge_chunk; this helper
+        simply runs them back to back. A refused chunk raises MergeRefused with the number of
+        records already merged; those stay merged (a merge is not undone)."""
+        chunk = chunk or min(SNAP_CHUNK, int(self.cfg.max_batch_desc))
+        total = dict.fromkeys(MERGE_REPORT_FIELDS, 0)
+        if not records.shape[0]:
+            return self.merge_chunk(header, records, now)  # validates the header
+        for i in range(0, records.shape[0], chunk):
+            try:
+                rep = self.merge_chunk(header, records[i:i + chunk], now)
+            except RedisError as ex:
+                raise MergeRefused(str(ex), ex.code, i, total) from ex
+            for f in MERGE_REPORT_FIELDS:
+                total[f] += rep[f]
+        return total
+
+    def merge(self, path, now: int, first_record: int = 0) -> dict:
+        """Merge a snapshot file written by save() / write_snapshot(), streamed in chunks, from
+        record `first_record` on (to resume after a refusal and a resize). ValueError for a
+        malformed file (nothing changed); MergeRefused as merge_records."""
+        size = os.path.getsize(path)
+        chunk = min(SNAP_CHUNK, int(self.cfg.max_batch_desc))
+        total = dict.fromkeys(MERGE_REPORT_FIELDS, 0)
+        with open(path, "rb") as f:
+            h = _snapshot_header_from(f.read(SNAP_HEADER_BYTES))
+            if size != SNAP_HEADER_BYTES + SNAP_RECORD_BYTES * h.n_records:
+                raise ValueError(f"snapshot: file holds {size} bytes, its header says "
+                                 f"{SNAP_HEADER_BYTES} + {SNAP_RECORD_BYTES} * {h.n_records}")
+            if not 0 <= first_record <= h.n_records:
+                raise ValueError(f"snapshot: first_record {first_record} outside the file's {h.n_records} records")
+            f.seek(SNAP_HEADER_BYTES + SNAP_RECORD_BYTES * first_record)
+            done, left = first_record, int(h.n_records) - first_record
+            if not left:
+                return self.merge_chunk(h, np.zeros(0, SNAP_DTYPE), now)
+            while left:
+                part = np.fromfile(f, SNAP_DTYPE, min(left, chunk))
+                if not part.shape[0]:
+                    raise ValueError("snapshot: file shorter than its header says")
+                try:
+                    rep = self.merge_chunk(h, part, now)
+                except RedisError as ex:
+                    raise MergeRefused(str(ex), ex.code, done, total) from ex
+                for k in MERGE_REPORT_FIELDS:
+                    total[k] += rep[k]
+                done += part.shape[0]
+                left -= part.shape[0]
+        return total
+
     def stats(self) -> dict:
         s = RlEngineStats()
         self._check(self.lib.rl_get_stats(self.h, C.byref(s)), "rl_get_stats")
@@ -1365,6 +1447,12 @@ class HipRateLimitCache:
     def load(self, path):
         """Restore the counters from a snapshot file (Engine.load)."""
         return self.engine.load(path)
+
+    def merge(self, path, first_record: int = 0) -> dict:
+        """Fold a snapshot file into the live counters (Engine.merge) at the time source's now:
+        counters add, expiries take the later one. The cache keeps serving: DoLimit calls between
+        two chunks are decided between them."""
+        return self.engine.merge(path, self.time_source(), first_record)
 
     def resize(self, log2_slots):
         """Resize the counter table on the device (Engine.resize); 0 keeps a unit's size."""

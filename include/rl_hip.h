@@ -622,6 +622,87 @@ int rl_restore_begin(rl_engine* e, const rl_snapshot_header* hdr);
 int rl_restore_put(rl_engine* e, const void* host_recs, uint32_t n);
 int rl_restore_end(rl_engine* e);
 
+/* ---- Merge ------------------------------------------------------------------
+ * Fold records of a snapshot into a table that is already serving: counters add, expiries and
+ * local-cache deadlines take the later of the two, absent identities are claimed. Three uses:
+ * a restarted process that answers at once and takes its last snapshot afterwards; the per-rank
+ * snapshots of a routed deployment consolidated into one engine (records carry no key string and
+ * need none); a blue/green handover, the new process taking the old one's counters while it
+ * already serves. No counterpart in the reference, whose counters live in Redis.
+ *
+ * The call is stateless and synchronous and runs between batches: one call takes one chunk of a
+ * snapshot's records from host memory (staged through the restore's bounded pinned memory), in
+ * any order and in chunks of any size; there is no begin / end, so nothing stays open. The same
+ * record in two calls adds twice: a caller must not repeat a chunk that was applied.
+ *
+ * Header: validated on every call as rl_restore_begin validates it (magic, header_bytes,
+ * record_bytes, reserved words, seed_check against this engine's hash_seed, RL_SNAP_SPLIT against
+ * per_second_split; RL_EINVAL otherwise). RL_SNAP_LAG and RL_SNAP_LOCAL_CACHE may differ: the
+ * records are judged by this engine's rules. n_records and the per-region counts are not used (a
+ * chunk is a subset).
+ *
+ * Records, checked on the host before anything is staged: RL_EINVAL for a generation of 0, for a
+ * (region, generation) no engine writes (the window start of the generation in that region must
+ * have exactly that region and generation as its place, and must not be above 0xFFFD0000), and
+ * for now outside [0, 0xFFFD0000].
+ *
+ * Target generation per region: T[r] = max(rl_occupancy.gen[r], the largest generation among
+ * this call's records of region r that leave something). A record of generation g applies as
+ * newest when g == T[r], as previous when r is a lag region of this engine and g + 2 == T[r], and
+ * is over otherwise (dropped_over). A snapshot newer than the table so advances the region
+ * exactly as a batch does (the older slots turn stale); one older than the table is dropped.
+ *
+ * A record leaves something when now < exp, or pcount != 0, or this engine's local cache is on
+ * and now < frz. Any other record is dropped_empty and claims nothing, even when its identity is
+ * present.
+ *
+ * Fold, slot state S (zeros for a fresh claim) and record R, aR = now < R.exp, aS = found &&
+ * now < S.exp:  aR && aS: count = S.count + R.count (mod 2^32, the counter's own width), exp =
+ * max(S.exp, R.exp);  aR && !aS: count = R.count, exp = R.exp;  !aR: both words stay.
+ * pcount = S.pcount + R.pcount (mod 2^32);  frz = max(S.frz, R.frz). For a caller: rl_peek at
+ * `now` after the merge answers, for every key string, the sum of the counts, the larger TTL and
+ * the larger cached seconds of what rl_peek at `now` answered on the two sides. That equals one
+ * server that saw both histories when every string is counted under one unit, there is no EXPIRE
+ * jitter, and the snapshot's touches are not later than the table's. With jitter the expiry is the
+ * maximum rather than the last one; a string shared by rules of different units can differ where
+ * an expiry falls between the two histories, which neither side can tell. The local cache is only
+ * a cache, as the reference's freecache: a string over its limit only in the sum is not frozen
+ * until its next INCRBY.
+ *
+ * Atomic per call, refused before anything changes (table, occupancy, stats and *report are then
+ * untouched; after rl_resize the same chunk can be passed again):
+ *   RL_ESTATE     a batch in flight, a restore open, or a routed-set plan open (an open snapshot
+ *                 does not block)
+ *   RL_ECAPACITY  n above max_batch_desc, or max_batch_desc above 2^29
+ *   RL_EINVAL     the header and record checks above; one identity (claim word, key) twice in
+ *                 the call (found by the planning pass on the device)
+ *   RL_EDEVICE    two identities of the call share one 64-bit sort key: split the call (as rl_set)
+ *   RL_ENOSPC     per region, the slots a key of generation T[r] cannot take plus the call's exact
+ *                 number of absent identities that apply and leave something pass the load limit
+ *   RL_EHIP       any HIP failure before the applying pass
+ * A failure of the applying pass itself (RL_EHIP, or RL_EDEVICE for a region without a free slot,
+ * which the RL_ENOSPC check rules out) may leave part of the call in the table.
+ *
+ * Occupancy: claims are counted per (region, class) on the device and enter the occupancy as a
+ * batch's do, the newest class at T[r] and the previous class at T[r] - 2; inserted_keys grows by
+ * the claims and live_keys follows. A region where the call claims nothing keeps its occupancy.
+ * The hot set and the candidate stash are untouched. n == 0 validates the header and returns 0.
+ *
+ * Not provided: a router-level call (records carry no owner: merging is for consolidating into
+ * one engine, or for a rank taking back its own snapshot, which this call on a router's engine
+ * between steps already does), a device-memory form, and undoing a merge. */
+typedef struct rl_merge_report {   /* 64 B */
+  uint64_t records;        /* n of the call */
+  uint64_t folded;         /* identity found in the table: the record's state folded into its slot */
+  uint64_t claimed;        /* identity absent: a slot claimed, the record's state written */
+  uint64_t dropped_over;   /* its window generation is over in this table */
+  uint64_t dropped_empty;  /* it leaves nothing at `now` (looked at after dropped_over) */
+  uint64_t reserved[3];    /* 0 */
+} rl_merge_report;         /* records == folded + claimed + dropped_over + dropped_empty */
+
+int rl_merge(rl_engine* e, const rl_snapshot_header* hdr, const void* host_recs, uint32_t n,
+             int64_t now, rl_merge_report* report_or_null);
+
 /* ---- Resize ---------------------------------------------------------------
  * Resize the counter table in place: log2_slots[u] slots per window generation for home unit u
  * (0 = keep that unit's size). Every live slot ("What is live" above) keeps its claim word, key,
