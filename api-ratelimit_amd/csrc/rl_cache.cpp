@@ -395,12 +395,14 @@ void HipRateLimitCache::finish_oldest(std::deque<Staged>& inflight) {
 // Peek / Forget / Set: the request's descriptors as one rl_batch of one request, built and handed
 // to rl_peek / rl_forget / rl_set by the submitter thread (a control call), at the time it reads
 // there. values != nullptr: a Set, with `keep` (RL_SET_KEEP_*) or-ed into every value's flags.
+// deltas != nullptr: an Adjust, with `keep` as rl_adjust's flags.
 std::vector<HipRateLimitCache::PeekStatus> HipRateLimitCache::peek_call(
     const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits, bool forget,
-    const std::vector<PeekStatus>* values, uint32_t keep) {
+    const std::vector<PeekStatus>* values, uint32_t keep, const std::vector<int32_t>* deltas) {
   if (request.Descriptors.size() != limits.size())
     throw std::logic_error("assert: len(request.Descriptors) == len(limits)");
   if (values && values->size() != limits.size()) throw std::logic_error("assert: len(values) == len(limits)");
+  if (deltas && deltas->size() != limits.size()) throw std::logic_error("assert: len(deltas) == len(limits)");
   const size_t n = limits.size();
   // GenerateCacheKey prefixes (cache_key.go:57-65), on the caller's thread
   std::vector<uint8_t> blob;
@@ -443,7 +445,10 @@ std::vector<HipRateLimitCache::PeekStatus> HipRateLimitCache::peek_call(
     b.req_of = req_of.data();
     b.now = &now;
     std::vector<rl_peek_reply> rep(n);
-    if (values) {
+    if (deltas) {
+      // nothing is claimed: the auto-grow check does not run behind it
+      if (rl_adjust(eng_, &b, deltas->data(), keep, rep.data(), nullptr)) return rl_last_error(eng_);
+    } else if (values) {
       std::vector<rl_peek_reply> val(n);
       for (size_t i = 0; i < n; ++i) {
         const PeekStatus& v = (*values)[i];
@@ -487,6 +492,13 @@ std::vector<HipRateLimitCache::PeekStatus> HipRateLimitCache::Set(
   const uint32_t keep = (keep_counter ? (uint32_t)RL_SET_KEEP_COUNTER : 0u) |
                         (keep_cache || fc_ ? (uint32_t)RL_SET_KEEP_CACHE : 0u);
   return peek_call(request, limits, false, &values, keep);
+}
+
+std::vector<HipRateLimitCache::PeekStatus> HipRateLimitCache::Adjust(
+    const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits,
+    const std::vector<int32_t>& deltas, bool keep_cache) {
+  // HIP_LOCAL_CACHE=freecache: the device cache is unused, the cache part is ignored
+  return peek_call(request, limits, false, nullptr, keep_cache || fc_ ? (uint32_t)RL_ADJUST_KEEP_CACHE : 0u, &deltas);
 }
 
 DoLimitResponse HipRateLimitCache::DoLimit(const RateLimitRequest& request,

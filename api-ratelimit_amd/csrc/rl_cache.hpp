@@ -254,6 +254,21 @@ class HipRateLimitCache : public RateLimitCache {
                               const std::vector<PeekStatus>& values, bool keep_counter = false,
                               bool keep_cache = false);
 
+  // Adjust (rl_hip.h "Adjust"): Redis INCRBY / DECRBY by key outside a decision, per descriptor of
+  // a request as DoLimit would key it: deltas[i] (signed: a refund is negative, a true-up either)
+  // is added to descriptor i's counter where it exists at the call's time, clamped to
+  // [0, 2^32 - 1]; a counter that is absent (its window is over) is left alone and nothing is
+  // claimed. A refund that brings the key back to its limit releases it from the device local cache
+  // unless keep_cache. Returns what Peek would have returned just before. No hit, no stat, no
+  // decision. A control call exactly like Forget: every DoLimit enqueued before it is decided
+  // first, the time is taken on the submitter thread, the trace hook reports kTraceControl, new
+  // (RequestsPerUnit, unit) pairs are registered as DoLimit registers them. The auto-grow check
+  // does not run behind it (nothing is claimed). HIP_LOCAL_CACHE=freecache: the cache part is
+  // ignored, as the device cache is unused there (a host entry expires after at most one divider).
+  // Errors throw RedisError. HipRoutedRateLimitCache has no Adjust (rl_hip.h "Adjust", out of scope).
+  std::vector<PeekStatus> Adjust(const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits,
+                                 const std::vector<int32_t>& deltas, bool keep_cache = false);
+
   // Resize (rl_hip.h "Resize"): the counter table moved into one of log2_slots[u] slots per window
   // generation for home unit u (0 keeps that unit's size), on the device, every counter kept. A
   // control call like Save / Load: every DoLimit enqueued before it is decided first, rl_resize
@@ -331,7 +346,8 @@ class HipRateLimitCache : public RateLimitCache {
   void control(std::function<std::string()> f);
   std::vector<PeekStatus> peek_call(const RateLimitRequest& request,
                                     const std::vector<std::shared_ptr<RateLimit>>& limits, bool forget,
-                                    const std::vector<PeekStatus>* values = nullptr, uint32_t keep = 0);
+                                    const std::vector<PeekStatus>* values = nullptr, uint32_t keep = 0,
+                                    const std::vector<int32_t>* deltas = nullptr);
   bool grow_after_ctl_ = false;  // set by a Set's control call, read by the submitter behind it
   uint32_t rule_id(const RateLimitLimit& l, bool shadow);
   bool fits(const Staged& st, const PendingCall& c) const;

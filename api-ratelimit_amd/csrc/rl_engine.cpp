@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "rl_adjust.h"
 #include "rl_census.h"
 #include "rl_common.h"
 #include "rl_hip.h"
@@ -95,14 +96,15 @@ namespace {
 enum KernelId {
   KT_FINGERPRINT, KT_HISTOGRAM, KT_HIST_SCAN, KT_SORT_PASS, KT_SCAN, KT_LEADER, KT_DECIDE, KT_FALLBACK, KT_MEMSET,
   KT_CAND, KT_V4_HIST, KT_V4_SCAN, KT_V4_PLACE, KT_V4_GROUP, KT_RESOLVE, KT_RULE_STATS, KT_CACHE_STATS, KT_CENSUS,
-  KT_SET_INDEX, KT_SET_PLAN, KT_SET_APPLY, KT_SET_INDEX_ROUTED, KT_MERGE_PLAN, KT_MERGE_APPLY, KT_COUNT
+  KT_SET_INDEX, KT_SET_PLAN, KT_SET_APPLY, KT_SET_INDEX_ROUTED, KT_MERGE_PLAN, KT_MERGE_APPLY,
+  KT_ADJUST_INDEX, KT_ADJUST_APPLY, KT_COUNT
 };
 const char* const kKernelNames[KT_COUNT] = {"k_fingerprint", "k_histogram", "k_hist_scan", "k_sort_pass", "k_scan",
                                             "k_leader",      "k_decide",    "fallback",    "memset",      "k_cand_state",
                                             "k4_hist",       "k4_scan",     "k4_place",    "k4_group",
                                             "k_resolve",     "k_rule_stats", "k_cache_stats", "k_census",
                                             "k_set_index",   "k_set_plan",  "k_set_apply", "k_set_index_routed",
-                                            "k_merge_plan",  "k_merge_apply"};
+                                            "k_merge_plan",  "k_merge_apply", "k_adjust_index", "k_adjust_apply"};
 
 enum Mode { MODE_LSD = 1, MODE_LSD_FULL = 2, MODE_V4 = 4 };
 
@@ -171,6 +173,10 @@ struct rl_engine {
   rl_peek_reply* d_set_vals = nullptr;
   SetCtl* h_set_ctl = nullptr;
   int set_ensure();
+  // rl_adjust (rl_adjust.h) runs in rl_set's scratch; its replies pass through pinned memory of
+  // their own (16 B x max_batch_desc, allocated at the first call that asks for them and kept), so
+  // that a refused call leaves the caller's array alone
+  rl_peek_reply* h_adj_rep = nullptr;
   // a routed set's plan between rl_set_routed_plan and rl_set_routed_commit: its records, its
   // scratch view, its window generation per region. While it is open the engine refuses what an
   // open restore refuses (set_busy).
@@ -1324,6 +1330,7 @@ void rl_destroy(rl_engine* e) {
   hipHostFree(e->h_route);
   hipHostFree(e->h_census);
   hipHostFree(e->h_set_ctl);
+  hipHostFree(e->h_adj_rep);
   hipHostFree(e->h_merge_ctl);
   for (hipStream_t s : {e->front, e->xin, e->xout, e->own_stream})
     if (s) hipStreamDestroy(s);
@@ -2743,6 +2750,86 @@ int rl_set_routed_commit(rl_engine* e, int apply) {
   e->set_open = false;
   if (!apply || !e->set_plan_n) return 0;
   return set_apply(e, "rl_set_routed_commit", e->set_plan_n, e->set_plan_sc, e->set_plan_gen, nullptr, nullptr);
+}
+
+// ---- Adjust ---------------------------------------------------------------------------------
+// rl_adjust: rl_set's checks in rl_set's order, then the staging, the two launches and one stream
+// synchronise. The index and the control block live in rl_set's scratch (both calls are
+// synchronous and an open plan is refused), the deltas in its staged-value array. k_adjust_index
+// writes nothing to the table and k_adjust_apply nothing after an index overflow, so every
+// failure reported below is one before anything changed.
+int rl_adjust(rl_engine* e, const rl_batch* b, const int32_t* delta, uint32_t flags, rl_peek_reply* out,
+              rl_adjust_report* report) {
+  if (!e || !b) return RL_EINVAL;
+  int rc = peek_enter(e, b, "rl_adjust", true);
+  if (rc) return rc;
+  if (e->cfg.max_batch_desc > SET_MAX_DESC)
+    return e->fail(RL_ECAPACITY, "rl_adjust: max_batch_desc %u above 2^29", e->cfg.max_batch_desc);
+  if (b->n_desc && !delta) return e->fail(RL_EINVAL, "rl_adjust: null delta array");
+  if (flags & ~(uint32_t)RL_ADJUST_KEEP_CACHE) return e->fail(RL_EINVAL, "rl_adjust: unknown flag bits 0x%x", flags);
+  rc = peek_check(e, b, "rl_adjust");
+  if (rc) return rc;
+  rl_adjust_report rep;
+  memset(&rep, 0, sizeof rep);
+  if (!b->n_desc) {
+    if (report) *report = rep;
+    return 0;
+  }
+  rc = e->set_ensure();
+  if (rc) return rc;
+  if (out && !e->h_adj_rep) {
+    const size_t n = e->cfg.max_batch_desc ? e->cfg.max_batch_desc : 1u;
+    const hipError_t ha = hipHostMalloc(&e->h_adj_rep, n * sizeof(rl_peek_reply), hipHostMallocDefault);
+    if (ha != hipSuccess) {
+      (void)hipGetLastError();
+      e->h_adj_rep = nullptr;
+      return e->hip_fail(ha, "rl_adjust reply staging allocation");
+    }
+  }
+  rl_batch d;
+  rl_peek_reply* d_rep = nullptr;
+  rc = peek_stage(e, b, d, d_rep);
+  if (rc) return rc;
+  static_assert(sizeof(int32_t) <= sizeof(rl_peek_reply), "the deltas fit the staged-value array");
+  int32_t* d_delta = reinterpret_cast<int32_t*>(e->d_set_vals);
+  AdjScratch sc;
+  sc.index = reinterpret_cast<AdjEntry*>(e->set_sc.index);
+  sc.ctl = reinterpret_cast<AdjCtl*>(e->set_sc.ctl);
+  sc.log2_entries = 6;
+  while ((1ull << sc.log2_entries) < 2ull * b->n_desc) ++sc.log2_entries;  // <= the allocation's: n <= max_batch_desc
+  AdjCtl* hc = reinterpret_cast<AdjCtl*>(e->h_set_ctl);
+  hipError_t he = hipMemcpyAsync(d_delta, delta, (size_t)b->n_desc * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipMemsetAsync(sc.index, 0, sizeof(AdjEntry) << sc.log2_entries, e->stream);
+  if (he == hipSuccess) he = hipMemsetAsync(sc.ctl, 0, sizeof(AdjCtl), e->stream);
+  if (he != hipSuccess) return e->hip_fail(he, "rl_adjust (nothing written)");
+  e->timed(KT_ADJUST_INDEX, [&] {
+    launch_adjust_index(e->stream, d, e->d_rules, e->n_rules, e->cfg.hash_seed, e->tab, d_delta, out ? d_rep : nullptr,
+                        sc);
+  });
+  he = hipGetLastError();
+  if (he != hipSuccess) return e->hip_fail(he, "rl_adjust (nothing written)");
+  const bool clear_cache = e->tab.local_cache && !(flags & RL_ADJUST_KEEP_CACHE);
+  e->timed(KT_ADJUST_APPLY, [&] { launch_adjust_apply(e->stream, clear_cache, sc); });
+  he = hipGetLastError();
+  if (he == hipSuccess) he = hipMemcpyAsync(hc, sc.ctl, sizeof(AdjCtl), hipMemcpyDeviceToHost, e->stream);
+  // the replies land in pinned memory first: a refused call leaves `out` as it was
+  rl_peek_reply* h_rep = e->h_adj_rep;
+  if (he == hipSuccess && out)
+    he = hipMemcpyAsync(h_rep, d_rep, (size_t)b->n_desc * sizeof(rl_peek_reply), hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  if (he != hipSuccess) return e->hip_fail(he, "rl_adjust: applying pass (the table may hold part of the call)");
+  if (e->timing) e->fold_marks();
+  if (hc->w[ADJ_ERR][0]) return e->fail(RL_EDEVICE, "rl_adjust: the call's index overflowed (nothing written)");
+  if (out) memcpy(out, h_rep, (size_t)b->n_desc * sizeof(rl_peek_reply));
+  rep.descriptors = b->n_desc;
+  rep.nil = hc->w[ADJ_NIL][0];
+  rep.absent = hc->w[ADJ_ABSENT][0];
+  rep.applied = hc->w[ADJ_APPLIED][0];
+  rep.floored = hc->w[ADJ_FLOORED][0];
+  rep.capped = hc->w[ADJ_CAPPED][0];
+  rep.unfrozen = hc->w[ADJ_UNFROZEN][0];
+  if (report) *report = rep;
+  return 0;
 }
 
 int rl_peek_device(rl_engine* e, const rl_batch* b, rl_peek_reply* d_out) {

@@ -1,6 +1,7 @@
 // rl_peek.h — the lookup both peek kernels end in (rl_peek.hip k_peek: from a descriptor;
 // rl_peek_routed.hip k_peek_routed: from a routed record), one function so the two cannot drift,
-// and the key identity it starts from, which rl_set.hip shares.
+// and the key identity it starts from, which rl_set.hip shares; and that lookup's sibling that
+// also hands back the slot (rl_adjust.hip).
 #pragma once
 #include "rl_decide.h"
 
@@ -80,6 +81,42 @@ __device__ __forceinline__ rl_peek_reply peek_key(const FpState& s, const uint32
       slot->exp = 0u;
     }
     slot->frz = 0u;
+  }
+  return rep;
+}
+
+// peek_key<false>'s lookup and reply for a caller that then writes the counter it found
+// (rl_adjust.hip): `found` is the string's slot when the reply says RL_PEEK_FOUND and nullptr
+// otherwise, ps the descriptor's store. A sibling rather than a parameter of peek_key: k_peek was
+// measured sensitive to that function's shape.
+__device__ __forceinline__ rl_peek_reply peek_key_slot(const FpState& s, const uint32_t n32, const DevRule& rr,
+                                                       const TableDesc& tab, rl_peek_reply rep, Slot*& found,
+                                                       bool& ps) {
+  const KeyIdent id = key_ident(s, n32, rr);
+  const SlotView pre = load_slot(slot_first(tab, id.key));
+  Slot* slot = nullptr;
+  KeyState st{0, 0, 0, 0};
+  const bool have = table_find(tab, id.key, id.lo, id.pl.gen, pre, slot, st);
+  ps = per_second_store(tab, rr.unit);
+  found = nullptr;
+  rep.flags = ps ? RL_PEEK_PER_SECOND : 0u;
+  if (have) {
+    if (ps) {
+      if (st.pcount) {
+        rep.flags |= RL_PEEK_FOUND;
+        rep.count = st.pcount;
+        found = slot;
+      }
+    } else if (n32 < st.exp) {
+      rep.flags |= RL_PEEK_FOUND;
+      rep.count = st.count;
+      rep.ttl_s = st.exp - n32;
+      found = slot;
+    }
+    if (tab.local_cache && n32 < st.frz) {
+      rep.flags |= RL_PEEK_LOCAL_CACHED;
+      rep.cached_s = st.frz - n32;
+    }
   }
   return rep;
 }

@@ -120,6 +120,12 @@ PEEK_FOUND, PEEK_LOCAL_CACHED, PEEK_NIL, PEEK_PER_SECOND, PEEK_BAD = 1, 2, 4, 8,
 PEEK_DTYPE = np.dtype([("count", "<u4"), ("ttl_s", "<u4"), ("cached_s", "<u4"), ("flags", "<u4")])
 SET_KEEP_COUNTER, SET_KEEP_CACHE = 32, 64  # RL_SET_KEEP_*: rl_set's input-only bits of rl_peek_reply.flags
 PEEK_ROUTED_FORGET = 1  # RL_PEEK_ROUTED_FORGET: rl_peek_routed clears after it has looked every record up
+ADJUST_KEEP_CACHE = 1  # RL_ADJUST_KEEP_CACHE: rl_adjust leaves every local-cache deadline as it is
+ADJUST_REPORT_FIELDS = ("descriptors", "nil", "absent", "applied", "floored", "capped", "unfrozen")
+
+
+class RlAdjustReport(C.Structure):  # rl_adjust_report, 64 B
+    _fields_ = [(f, C.c_uint64) for f in ADJUST_REPORT_FIELDS] + [("reserved", C.c_uint64)]
 
 
 # ---- rule stats (rl_hip.h "Rule stats") ----
@@ -304,6 +310,8 @@ ABI = [
     ("rl_peek_device", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
     ("rl_forget", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
     ("rl_set", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_void_p], C.c_int),
+    ("rl_adjust", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(RlAdjustReport)],
+     C.c_int),
     ("rl_peek_routed", [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32], C.c_int),
     ("rl_route_unpack_peek", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     ("rl_router_peek", [C.c_void_p, C.POINTER(RlBatch), C.POINTER(C.c_void_p)], C.c_int),
@@ -813,6 +821,25 @@ class Engine:
         self._check(self.lib.rl_set(self.h, C.byref(s), _ptr(values) or None,
                                     (_ptr(out) or None) if want_out else None), "rl_set")
         return out
+
+    def adjust(self, b: Batch, delta, keep_cache: bool = False, want_out: bool = True):
+        """rl_adjust of a host batch (hits and jitter ignored): delta[i] (int32) is added to descriptor
+        i's counter where it is found, summed per (string, store) and clamped to [0, 2^32 - 1] once;
+        a refund that brings a key back to its limit drops its local-cache entry unless keep_cache.
+        Nothing is claimed. Returns (the replies as read before the call (PEEK_DTYPE) or None, the
+        report as a dict of ADJUST_REPORT_FIELDS)."""
+        d = np.asarray(delta)
+        if d.shape != (b.n_desc,):
+            raise ValueError(f"rl_adjust: {d.shape[0] if d.ndim == 1 else d.shape} deltas for {b.n_desc} descriptors")
+        if d.size and (d.dtype.kind not in "iu" or int(d.min()) < -2**31 or int(d.max()) > 2**31 - 1):
+            raise ValueError("rl_adjust: a delta is not an int32")
+        d = np.ascontiguousarray(d, np.int32)
+        out = np.zeros(b.n_desc, PEEK_DTYPE) if want_out else None
+        rep = RlAdjustReport()
+        s = _batch_struct(b)
+        self._check(self.lib.rl_adjust(self.h, C.byref(s), _ptr(d) or None, ADJUST_KEEP_CACHE if keep_cache else 0,
+                                       (_ptr(out) or None) if want_out else None, C.byref(rep)), "rl_adjust")
+        return out, {f: int(getattr(rep, f)) for f in ADJUST_REPORT_FIELDS}
 
     def peek_device(self, n_desc: int, n_req: int, blob_bytes: int, ptrs, out_ptr: int):
         """rl_peek_device: an rl_batch of device pointers (ptrs = blob, off, rule, req_of, now, hits
@@ -1473,6 +1500,20 @@ class HipRateLimitCache:
         v["flags"] |= (SET_KEEP_COUNTER if keep_counter else 0) | (SET_KEEP_CACHE if keep_cache else 0)
         b = build_batch([(request.Domain, request.Descriptors, rules, request.HitsAddend, self.time_source())])
         return self.engine.set(b, v)
+
+    def adjust(self, request: RateLimitRequest, limits: list, deltas, keep_cache: bool = False):
+        """HipRateLimitCache::Adjust (rl_cache.hpp): deltas[i] (signed) is added to descriptor i's
+        counter at the time source's now, where the counter exists; a refund (negative) that brings
+        the key back to its limit releases it from the local cache unless keep_cache. Returns the
+        replies as read before the call. Spends nothing: no hit, no stat, no decision."""
+        assert len(request.Descriptors) == len(limits), "assert: len(request.Descriptors) == len(limits)"
+        assert len(deltas) == len(limits), "assert: len(deltas) == len(limits)"
+        rules = [NIL_RULE if lim is None else self._rule(lim.Limit, lim.ShadowMode) for lim in limits]
+        if self.dirty:
+            self.engine.load_rules(self.rules)
+            self.dirty = False
+        b = build_batch([(request.Domain, request.Descriptors, rules, request.HitsAddend, self.time_source())])
+        return self.engine.adjust(b, np.array(deltas, np.int64).reshape(len(limits)), keep_cache=keep_cache)[0]
 
     def do_limit_batch(self, calls) -> list:
         reqs = []

@@ -865,6 +865,85 @@ int rl_forget(rl_engine* e, const rl_batch* host_batch, rl_peek_reply* out_or_nu
 enum { RL_SET_KEEP_COUNTER = 32u, RL_SET_KEEP_CACHE = 64u }; /* rl_peek_reply.flags, input only */
 int rl_set(rl_engine* e, const rl_batch* host_batch, const rl_peek_reply* values, rl_peek_reply* out_or_null);
 
+/* ---- Adjust: signed counter corrections by key -------------------------------
+ * Redis INCRBY / DECRBY by key, outside a decision: what a cost limiter (hits_addend as tokens,
+ * bytes, credits) needs to give a charge back (a refund: the request failed downstream, was
+ * rejected by a later stage or was cancelled) and to replace an estimate by the real cost (a
+ * true-up, positive or negative). A submit can only add, and rl_peek + rl_set(KEEP_CACHE) is a
+ * read-modify-write through the host that loses every increment in between and cannot sum two
+ * corrections of one key in one call. host_batch is an ordinary batch, read exactly as rl_peek
+ * reads it (hits_addend and ttl_jitter ignored, may be NULL; req_of and now give descriptor i its
+ * time t); delta[i] is descriptor i's signed correction. Host memory, synchronous, between batches.
+ * No decision, no stat increment and no local-cache hit comes of it.
+ *
+ * Store and identity: rl_peek's. The key string is prefix || decimal window start under the rule's
+ * unit; the store is the main or the per-second one by rl_config.per_second_split.
+ * Found: rl_peek's RL_PEEK_FOUND at t, word for word. Main store: the string's slot exists for that
+ * window generation and t < its expiry; per-second store: the slot exists and its counter is not 0.
+ * Not found: the descriptor is `absent`: nothing is written and nothing is ever claimed. A
+ * correction belongs to the window that was charged; if that window is over, it is dropped. So
+ * occupancy, the host mirror, inserted_keys, live_keys, the hot set and the candidate stash never
+ * change, and RL_ENOSPC cannot occur.
+ *
+ * Sum per (string, store) pair: net = the 64-bit sum of delta[i] over the call's found descriptors
+ * of the pair, and new = clamp(count + net, 0, 0xFFFFFFFF), applied once per pair. The result
+ * depends on neither the descriptor order nor scheduling: a counter of 5 with deltas (-10, +3)
+ * ends at 0, not 3. The call is one atomic INCRBY net, not a pipeline of INCRBYs.
+ * Saturation at both ends is deliberate. Redis would go negative, and the reference decodes the
+ * reply as uint32, which would leave the key over its limit for its whole window; at the top a
+ * wrapped counter would forgive everything. The reference has no such command, so parity is
+ * unpinned here by construction.
+ * What is written, as separate 32-bit stores (two pairs may share one slot). Main store: count =
+ * new; the expiry is never touched, so a counter that reaches 0 keeps its TTL and reads back FOUND
+ * with count 0, as after DECRBY. Per-second store: counter = new; 0 is that store's "absent", so it
+ * reads back as not found.
+ *
+ * Cache part, only with rl_config.local_cache on and without RL_ADJUST_KEEP_CACHE: a pair qualifies
+ * when net < 0 and new <= the smallest requests_per_unit among the call's found descriptors of that
+ * pair; a string with at least one qualifying pair loses its local-cache deadline (set to 0), and
+ * `unfrozen` counts the strings whose deadline word was non-zero, each once. Without it a refunded
+ * key would stay OVER_LIMIT until its window ends. A positive net never freezes anything: the
+ * cache is only a cache, the next INCRBY freezes the key (rl_merge's rule).
+ *
+ * out (may be NULL) receives rl_peek's reply for every descriptor as of just before the call,
+ * duplicates included (rl_forget's rule); with every delta 0 the call is a peek. Untouched: rule
+ * stats, the cache-stats counters, the step clock and every field of rl_engine_stats.
+ *
+ * Report: descriptors == nil + absent + applied. floored / capped count the pairs whose count + net
+ * fell below 0 / rose above 0xFFFFFFFF and stopped there (a sum of exactly 0 is not floored).
+ *
+ * Refused before anything changes (table, out and *report untouched):
+ *   RL_ESTATE     a batch in flight, a restore open, or a routed-set plan open (an open snapshot
+ *                 does not block the call)
+ *   RL_ECAPACITY  rl_peek's capacity limits, or max_batch_desc above 2^29
+ *   RL_EINVAL     everything rl_peek refuses; delta == NULL with n_desc > 0; any flag bit other than
+ *                 RL_ADJUST_KEEP_CACHE
+ *   RL_EDEVICE    the scratch index had no entry left (unreachable: it has 2^k >= 2 n_desc entries);
+ *                 the applying pass then writes nothing
+ *   RL_EHIP       any HIP failure before the applying pass
+ * n_desc == 0 returns 0 and zeroes the report.
+ * Scratch: the call runs in rl_set's scratch (its index, 32 B x the power of two >= 2 x
+ * max_batch_desc, its control block, and its staged-value array for the 4 B x n_desc deltas), which
+ * is allocated at the first rl_set or rl_adjust and kept: both calls are synchronous and exclude each
+ * other, and an open routed-set plan, which lives there, refuses this one. The batch goes through
+ * rl_peek's free host staging slot; the replies pass through 16 B x max_batch_desc of pinned memory,
+ * allocated at the first call that asks for them.
+ * Out of scope: a router-level call, an engine-level form over routed records, a device-memory
+ * form, adjusting while batches are in flight, a compact wire form. */
+enum { RL_ADJUST_KEEP_CACHE = 1u };
+typedef struct rl_adjust_report {   /* 64 B */
+  uint64_t descriptors;  /* n_desc of the call */
+  uint64_t nil;          /* RL_NIL_RULE descriptors: nothing looked up */
+  uint64_t absent;       /* descriptors with a limit whose counter was not found: nothing written */
+  uint64_t applied;      /* descriptors whose counter was found: delta entered its pair's sum (delta 0 too) */
+  uint64_t floored;      /* (string, store) pairs whose result stopped at 0 */
+  uint64_t capped;       /* pairs whose result stopped at 0xFFFFFFFF */
+  uint64_t unfrozen;     /* strings whose non-zero local-cache deadline the call cleared */
+  uint64_t reserved;     /* 0 */
+} rl_adjust_report;      /* descriptors == nil + absent + applied */
+int rl_adjust(rl_engine* e, const rl_batch* host_batch, const int32_t* delta, uint32_t flags,
+              rl_peek_reply* out_or_null, rl_adjust_report* report_or_null);
+
 /* ---- Routed peek / forget --------------------------------------------------
  * The same lookups where the keys are spread over the shards of a router.
  *
