@@ -1,4 +1,5 @@
-// rl_adjust.h — what the engine (rl_engine.cpp) and the adjust kernels (rl_adjust.hip) share.
+// rl_adjust.h — what the engine (rl_engine.cpp) and the adjust kernels (rl_adjust.hip,
+// rl_adjust_routed.hip) share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,7 +18,8 @@ struct __attribute__((aligned(32))) AdjEntry {
   long long net;            // sum of the deltas (atomicAdd)
   uint32_t lim_c;           // ~(the smallest requests_per_unit): the minimum as an atomicMax, so that
                             // the zeroed entry is "none"
-  uint32_t n;               // descriptors of the pair
+  uint32_t n;               // descriptors of the pair; the record form: those that came without
+                            // RL_ADJUST_KEEP_CACHE (non-zero: the pair's cache part may run)
   uint32_t pad[2];
 };
 static_assert(sizeof(AdjEntry) == sizeof(SetEntry), "the adjust index lives in rl_set's index allocation");
@@ -31,6 +33,7 @@ struct AdjCtl {
 };
 static_assert(sizeof(AdjCtl) <= sizeof(SetCtl), "the adjust control block lives in rl_set's");
 constexpr uint32_t ADJ_ERR_INDEX = 1u;  // the index had no entry left for a pair (unreachable: 2^k >= 2 n)
+constexpr uint32_t ADJ_ERR_BADREC = 2u;  // the record form: a malformed record (rule id, time or rule word's upper bits)
 
 struct AdjScratch {
   AdjEntry* index;
@@ -43,6 +46,17 @@ struct AdjScratch {
 void launch_adjust_index(hipStream_t st, const rl_batch& b, const DevRule* rules, uint32_t n_rules, uint64_t seed,
                          const TableDesc& tab, const int32_t* delta, rl_peek_reply* out, const AdjScratch& sc);
 // clear_cache: the call's cache part is on (the local cache is on and RL_ADJUST_KEEP_CACHE is not set).
-void launch_adjust_apply(hipStream_t st, bool clear_cache, const AdjScratch& sc);
+// per_key: a pair's cache part also needs its entry's count to be non-zero (a routed plan's commit).
+void launch_adjust_apply(hipStream_t st, bool clear_cache, bool per_key, const AdjScratch& sc);
+
+// The record form (rl_adjust_routed.hip): n routed records (RRec) whose h word is the delta and
+// whose rule word's bit 16 is RL_ADJUST_KEEP_CACHE. out: n replies in device memory, or nullptr.
+// A malformed record sets ADJ_ERR_BADREC and indexes nothing. Launches nothing for n == 0.
+void launch_adjust_index_routed(hipStream_t st, const RRec* recs, uint32_t n, const DevRule* rules, uint32_t n_rules,
+                                const TableDesc& tab, rl_peek_reply* out, const AdjScratch& sc);
+// Origin: descriptor i's delta and the call's keep bit into its record's h and rule words (perm:
+// the strided form of the plain pack, or RL_ROUTE_LOCAL; cap: the records send has room for).
+void launch_adjust_pack(hipStream_t st, uint32_t n, uint32_t cap, const uint32_t* perm, const uint32_t* rule_id,
+                        const int32_t* delta, uint32_t keep, RRec* send);
 
 }  // namespace rlhip

@@ -4,6 +4,8 @@
 //                   to its (slot, store) pair's entry of the call's scratch index
 //   k_adjust_apply  one lane per index entry: count = clamp(count + net, 0, 2^32 - 1) as one 32-bit
 //                   store, and the string's local-cache deadline cleared where the pair qualifies
+// (adjust_key and block_add3 live in rl_adjust_key.h, shared with the record form of the first
+// kernel, rl_adjust_routed.hip)
 // The first kernel writes nothing to the table, so every reply is the state before the call; the
 // second writes each counter word from exactly one lane, so the result depends on neither the
 // descriptor order nor scheduling. Nothing is ever claimed. Kernel boundaries order the two: no
@@ -12,63 +14,11 @@
 #include <hip/hip_runtime.h>
 
 #include "rl_adjust.h"
+#include "rl_adjust_key.h"
 #include "rl_peek.h"
 
 namespace rlhip {
 namespace adjust {
-
-constexpr int NT = peek::NT;
-
-// Three flags summed over the block: a ballot per wave, the wave sums through LDS, then one add
-// per word and block on the word's own line. Every thread of the block calls it.
-RL_DEV void block_add3(const bool a, const bool b, const bool c, const int wa, const int wb, const int wc,
-                       AdjCtl* ctl) {
-  __shared__ uint32_t sh[NT / 64][3];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t ca = (uint32_t)__popcll(__ballot(a)), cb = (uint32_t)__popcll(__ballot(b)),
-                 cc = (uint32_t)__popcll(__ballot(c));
-  if (lane == 0u) {
-    sh[wave][0] = ca;
-    sh[wave][1] = cb;
-    sh[wave][2] = cc;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3u) {
-    uint32_t sum = 0;
-    for (int w = 0; w < NT / 64; ++w) sum += sh[w][threadIdx.x];
-    const int word = threadIdx.x == 0u ? wa : threadIdx.x == 1u ? wb : wc;
-    if (sum) atomicAdd(&ctl->w[word][0], sum);
-  }
-}
-
-// The lookup-and-accumulate step of one key: from its prefix state, its time t (in [0, MAX_NOW],
-// checked by the caller), its rule and its delta. rep goes in and out by value, as in peek_key.
-// Returns true when the counter was found (the delta entered its pair's sum). Every read of the
-// index probe is the CAS itself (rl_set_index.h: it returns the word from the L2).
-RL_DEV bool adjust_key(const FpState& s, const uint32_t t, const DevRule& rr, const int32_t delta,
-                       const TableDesc& tab, const AdjScratch& sc, rl_peek_reply& rep) {
-  Slot* slot = nullptr;
-  bool ps = false;
-  rep = peek::peek_key_slot(s, t, rr, tab, rep, slot, ps);
-  if (!slot) return false;
-  const unsigned long long pair = (unsigned long long)reinterpret_cast<uintptr_t>(slot) | (ps ? ADJ_PS : 0ull);
-  const uint32_t lg = sc.log2_entries;
-  const uint32_t mask = (1u << lg) - 1u;
-  uint32_t pos = (uint32_t)((pair * K0) >> (64 - lg));
-  for (uint32_t probe = 0; probe <= mask; ++probe) {
-    const unsigned long long old = atomicCAS(&sc.index[pos].pair, 0ull, pair);
-    if (old == 0ull || old == pair) {
-      AdjEntry* e = sc.index + pos;
-      if (delta) atomicAdd(reinterpret_cast<unsigned long long*>(&e->net), (unsigned long long)(long long)delta);
-      atomicMax(&e->lim_c, ~rr.L);
-      atomicAdd(&e->n, 1u);
-      return true;
-    }
-    pos = (pos + 1u) & mask;
-  }
-  atomicOr(&sc.ctl->w[ADJ_ERR][0], ADJ_ERR_INDEX);
-  return true;
-}
 
 // The loads go out as k_peek's do (rl_peek.hip): (offsets, rule id, request index, the delta),
 // then (now, the rule entry, the prefix's first 32 bytes), every one unconditional at a clamped
@@ -109,7 +59,7 @@ __global__ __launch_bounds__(NT) void k_adjust_index(const DevBatch in, const De
   bool applied = false;
   if (ok) {
     const FpState s = prefix_state_pre(w0, w1, in.blob, o0, len, seed);
-    applied = adjust_key(s, (uint32_t)now, rr, dl, tab, sc, rep);
+    applied = adjust_key<false>(s, (uint32_t)now, rr, dl, false, tab, sc, rep);
   }
   if (live && out) out[i] = rep;
   block_add3(live && nil, live && !nil && !applied, applied, ADJ_NIL, ADJ_ABSENT, ADJ_APPLIED, sc.ctl);
@@ -118,12 +68,17 @@ __global__ __launch_bounds__(NT) void k_adjust_index(const DevBatch in, const De
 // Entries are disjoint (one per (slot, store) pair), so a counter word is read and written by one
 // lane: plain loads and stores. The local-cache word is shared by a string's two pairs: atomicExch,
 // so that a deadline cleared by both counts once. After an index overflow nothing is written.
+// PER_KEY (a routed plan's commit, rl_adjust_routed.hip): a pair's cache part also needs the
+// entry's count, there "found records of the pair that came without RL_ADJUST_KEEP_CACHE", to be
+// non-zero; the host form's flag is the call's, folded into clear_cache.
+template <bool PER_KEY>
 __global__ __launch_bounds__(NT) void k_adjust_apply(const bool clear_cache, const AdjScratch sc) {
   const uint32_t i = blockIdx.x * NT + threadIdx.x;
   bool floored = false, capped = false, unfrozen = false;
   if (i < (1u << sc.log2_entries) && !sc.ctl->w[ADJ_ERR][0]) {
     const uint4 a = reinterpret_cast<const uint4*>(sc.index + i)[0];
     const uint2 b = reinterpret_cast<const uint2*>(sc.index + i)[2];
+    const bool release = !PER_KEY || b.y != 0u;
     const unsigned long long pair = (unsigned long long)a.x | ((unsigned long long)a.y << 32);
     if (pair) {
       const long long net = (long long)((unsigned long long)a.z | ((unsigned long long)a.w << 32));
@@ -136,7 +91,7 @@ __global__ __launch_bounds__(NT) void k_adjust_apply(const bool clear_cache, con
       capped = sum > 0xFFFFFFFFll;
       const uint32_t nw = floored ? 0u : capped ? 0xFFFFFFFFu : (uint32_t)sum;
       if (nw != cnt) *word = nw;
-      if (clear_cache && net < 0 && nw <= lim) unfrozen = atomicExch(&slot->frz, 0u) != 0u;
+      if (clear_cache && net < 0 && nw <= lim && release) unfrozen = atomicExch(&slot->frz, 0u) != 0u;
     }
   }
   block_add3(floored, capped, unfrozen, ADJ_FLOORED, ADJ_CAPPED, ADJ_UNFROZEN, sc.ctl);
@@ -152,9 +107,12 @@ void launch_adjust_index(hipStream_t st, const rl_batch& b, const DevRule* rules
   hipLaunchKernelGGL(adjust::k_adjust_index, dim3(grid), dim3(adjust::NT), 0, st, in, rules, n_rules, seed, tab, delta,
                      out, sc);
 }
-void launch_adjust_apply(hipStream_t st, bool clear_cache, const AdjScratch& sc) {
+void launch_adjust_apply(hipStream_t st, bool clear_cache, bool per_key, const AdjScratch& sc) {
   const uint32_t grid = ((1u << sc.log2_entries) + adjust::NT - 1u) / adjust::NT;
-  hipLaunchKernelGGL(adjust::k_adjust_apply, dim3(grid), dim3(adjust::NT), 0, st, clear_cache, sc);
+  if (per_key)
+    hipLaunchKernelGGL(adjust::k_adjust_apply<true>, dim3(grid), dim3(adjust::NT), 0, st, clear_cache, sc);
+  else
+    hipLaunchKernelGGL(adjust::k_adjust_apply<false>, dim3(grid), dim3(adjust::NT), 0, st, clear_cache, sc);
 }
 
 }  // namespace rlhip

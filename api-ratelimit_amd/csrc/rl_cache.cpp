@@ -60,11 +60,13 @@ struct PendingCall {
   // A control call (Save / Load) instead of a request: it keeps its place in the queue, and the
   // submitter runs it with nothing in flight. Returns an error message, empty on success.
   std::function<std::string()> ctl;
-  // HipRoutedRateLimitCache: a Peek (1), Forget (2) or Set (3) instead of a request, answered at a
-  // rule / stop agreement into `peek`; a Set's values (with its KEEP bits or-ed in) in `set_vals`
+  // HipRoutedRateLimitCache: a Peek (1), Forget (2), Set (3) or Adjust (4; 5 with keep_cache)
+  // instead of a request, answered at a rule / stop agreement into `peek`; a Set's values (with its
+  // KEEP bits or-ed in) in `set_vals`, an Adjust's deltas in `deltas`
   int kind = 0;
   std::vector<PeekStatus> peek;
   std::vector<rl_peek_reply> set_vals;
+  std::vector<int32_t> deltas;
 };
 
 namespace {
@@ -913,10 +915,11 @@ struct HipRoutedRateLimitCache::Step {
 
 namespace {
 // One rank's words in a rule / stop agreement (rl_router_allgather_host, RL_ROUTER_AG_MAX bytes).
-constexpr uint32_t SYNC_RULES = (RL_ROUTER_AG_MAX - 24) / sizeof(rl_rule);
+constexpr uint32_t SYNC_RULES = (RL_ROUTER_AG_MAX - 32) / sizeof(rl_rule);
 struct SyncWords {
   uint32_t stop, n;
-  uint32_t n_peek, n_forget, n_set, pad;  // pending Peek / Forget / Set calls of this rank
+  uint32_t n_peek, n_forget, n_set;  // pending Peek / Forget / Set calls of this rank
+  uint32_t n_adj, n_adj_keep, pad;   // pending Adjust calls without / with keep_cache
   rl_rule rules[SYNC_RULES];
 };
 static_assert(sizeof(SyncWords) <= RL_ROUTER_AG_MAX, "sync words");
@@ -1028,25 +1031,33 @@ bool HipRoutedRateLimitCache::known(const PendingCall& c) {
 // every rank's table in rank order (the first occurrence keeps its id), loaded into the engine.
 // Returns true when every rank asked to stop.
 // Then the control calls: if any rank has pending Peeks every rank makes one rl_router_peek, then
-// the same for Forgets, then for Sets (rl_router_set).
+// the same for Forgets, then for Sets (rl_router_set), then for Adjusts without keep_cache and for
+// Adjusts with it (rl_router_adjust: its flags word is per origin, hence the two calls).
 bool HipRoutedRateLimitCache::sync(bool want_stop, std::deque<std::shared_ptr<PendingCall>>& ctl, uint64_t seq) {
   SyncWords mine;
   memset(&mine, 0, sizeof mine);
   mine.stop = want_stop ? 1u : 0u;
-  for (const auto& c : ctl) (c->kind == 1 ? mine.n_peek : c->kind == 2 ? mine.n_forget : mine.n_set) += 1;
+  for (const auto& c : ctl)
+    (c->kind == 1   ? mine.n_peek
+     : c->kind == 2 ? mine.n_forget
+     : c->kind == 3 ? mine.n_set
+     : c->kind == 4 ? mine.n_adj
+                    : mine.n_adj_keep) += 1;
   mine.n = (uint32_t)std::min<size_t>(pending_.size(), SYNC_RULES);
   std::copy(pending_.begin(), pending_.begin() + mine.n, mine.rules);
   std::vector<SyncWords> all(r_.n_shards);
   int rc = rl_router_allgather_host(rt_, &mine, sizeof mine, all.data());
   if (rc) throw RedisError(std::string("rule agreement: ") + rl_router_last_error(rt_));
   n_syncs_ += 1;
-  bool all_stop = true, any_peek = false, any_forget = false, any_set = false;
+  bool all_stop = true, any_peek = false, any_forget = false, any_set = false, any_adj = false, any_adj_keep = false;
   const size_t before = rules_.size();
   for (const SyncWords& w : all) {
     all_stop &= w.stop != 0;
     any_peek |= w.n_peek != 0;
     any_forget |= w.n_forget != 0;
     any_set |= w.n_set != 0;
+    any_adj |= w.n_adj != 0;
+    any_adj_keep |= w.n_adj_keep != 0;
     for (uint32_t i = 0; i < w.n; ++i) {
       const auto k = std::make_pair(w.rules[i].requests_per_unit, w.rules[i].unit);
       if (ids_.emplace(k, (uint32_t)rules_.size()).second) rules_.push_back(w.rules[i]);
@@ -1063,10 +1074,13 @@ bool HipRoutedRateLimitCache::sync(bool want_stop, std::deque<std::shared_ptr<Pe
   if (any_peek) run_control(1, ctl, seq);
   if (any_forget) run_control(2, ctl, seq);
   if (any_set) run_control(3, ctl, seq);
+  if (any_adj) run_control(4, ctl, seq);
+  if (any_adj_keep) run_control(5, ctl, seq);
   return all_stop;
 }
 
-// One collective rl_router_peek (kind 1) / rl_router_forget (kind 2) / rl_router_set (kind 3) at an agreement: this rank's
+// One collective rl_router_peek (kind 1) / rl_router_forget (kind 2) / rl_router_set (kind 3) /
+// rl_router_adjust (kind 4; kind 5 with RL_ADJUST_KEEP_CACHE) at an agreement: this rank's
 // pending calls of the kind whose limits are agreed, in enqueue order, as one request each, as far
 // as one router batch holds them (the others wait for the following agreement); an empty batch
 // when there are none.
@@ -1076,6 +1090,7 @@ void HipRoutedRateLimitCache::run_control(int kind, std::deque<std::shared_ptr<P
   std::vector<uint32_t> off(1, 0u), rule, req_of;
   std::vector<int64_t> now;
   std::vector<rl_peek_reply> val;  // (a Set's)
+  std::vector<int32_t> dl;         // (an Adjust's)
   const size_t max_blob = (size_t)s_.batch_limit * 128u;
   for (auto it = ctl.begin(); it != ctl.end();) {
     PendingCall& c = **it;
@@ -1097,6 +1112,7 @@ void HipRoutedRateLimitCache::run_control(int kind, std::deque<std::shared_ptr<P
       req_of.push_back(rq);
     }
     val.insert(val.end(), c.set_vals.begin(), c.set_vals.end());
+    dl.insert(dl.end(), c.deltas.begin(), c.deltas.end());
     calls.push_back(*it);
     it = ctl.erase(it);
   }
@@ -1114,9 +1130,13 @@ void HipRoutedRateLimitCache::run_control(int kind, std::deque<std::shared_ptr<P
   rl_peek_reply* outs[1] = {rep.data()};
   val.resize(std::max<size_t>(1, val.size()));
   const rl_peek_reply* vals[1] = {val.data()};
+  dl.resize(std::max<size_t>(1, dl.size()));
+  const int32_t* dls[1] = {dl.data()};
+  const uint32_t flags[1] = {kind == 5 ? (uint32_t)RL_ADJUST_KEEP_CACHE : 0u};
   const int rc = kind == 1   ? rl_router_peek(rt_, &b, outs)
                  : kind == 2 ? rl_router_forget(rt_, &b, outs)
-                             : rl_router_set(rt_, &b, vals, outs);
+                 : kind == 3 ? rl_router_set(rt_, &b, vals, outs)
+                             : rl_router_adjust(rt_, &b, dls, flags, outs, nullptr);
   if (rc) {
     const std::string msg = rl_router_last_error(rt_);
     fail(calls, msg);
@@ -1145,11 +1165,13 @@ void HipRoutedRateLimitCache::run_control(int kind, std::deque<std::shared_ptr<P
 std::vector<PeekStatus> HipRoutedRateLimitCache::peek_call(const RateLimitRequest& request,
                                                            const std::vector<std::shared_ptr<RateLimit>>& limits,
                                                            int kind, const std::vector<PeekStatus>* values,
-                                                           uint32_t keep) {
+                                                           uint32_t keep, const std::vector<int32_t>* deltas) {
   if (request.Descriptors.size() != limits.size())
     throw std::logic_error("assert: len(request.Descriptors) == len(limits)");
   if (values && values->size() != limits.size()) throw std::logic_error("assert: len(values) == len(limits)");
+  if (deltas && deltas->size() != limits.size()) throw std::logic_error("assert: len(deltas) == len(limits)");
   auto call = std::make_shared<PendingCall>();
+  if (deltas) call->deltas = *deltas;
   if (values) {
     call->set_vals.resize(values->size());
     for (size_t i = 0; i < values->size(); ++i) {
@@ -1207,6 +1229,12 @@ std::vector<PeekStatus> HipRoutedRateLimitCache::Set(const RateLimitRequest& req
   const uint32_t keep = (keep_counter ? (uint32_t)RL_SET_KEEP_COUNTER : 0u) |
                         (keep_cache ? (uint32_t)RL_SET_KEEP_CACHE : 0u);
   return peek_call(request, limits, 3, &values, keep);
+}
+
+std::vector<PeekStatus> HipRoutedRateLimitCache::Adjust(const RateLimitRequest& request,
+                                                        const std::vector<std::shared_ptr<RateLimit>>& limits,
+                                                        const std::vector<int32_t>& deltas, bool keep_cache) {
+  return peek_call(request, limits, keep_cache ? 5 : 4, nullptr, 0, &deltas);
 }
 
 // The rank's step loop: rule / stop agreement every rule_sync_every steps (nothing in flight),

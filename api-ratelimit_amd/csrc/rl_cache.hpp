@@ -265,7 +265,8 @@ class HipRateLimitCache : public RateLimitCache {
   // (RequestsPerUnit, unit) pairs are registered as DoLimit registers them. The auto-grow check
   // does not run behind it (nothing is claimed). HIP_LOCAL_CACHE=freecache: the cache part is
   // ignored, as the device cache is unused there (a host entry expires after at most one divider).
-  // Errors throw RedisError. HipRoutedRateLimitCache has no Adjust (rl_hip.h "Adjust", out of scope).
+  // Errors throw RedisError. HipRoutedRateLimitCache has its own Adjust (below), applied at each
+  // key's owner.
   std::vector<PeekStatus> Adjust(const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits,
                                  const std::vector<int32_t>& deltas, bool keep_cache = false);
 
@@ -451,6 +452,19 @@ class HipRoutedRateLimitCache : public RateLimitCache {
                               const std::vector<PeekStatus>& values, bool keep_counter = false,
                               bool keep_cache = false);
 
+  // Adjust (rl_hip.h "Routed adjust"): HipRateLimitCache::Adjust's signature and PeekStatus, each
+  // correction applied at the owner of its key through rl_router_adjust, all owners or none; the
+  // corrections of one key from every rank of one agreement are summed and applied once. A further
+  // control kind beside Peek, Forget and Set: agreed at the rule / stop agreement and run after the
+  // agreement's Sets. rl_router_adjust's flags word is per origin, so every rank's agreement words
+  // carry two counts, its pending Adjusts without keep_cache and those with it, and they run as at
+  // most two router calls in that order: every rank's pending calls of the kind as one
+  // rl_router_adjust, one request each in enqueue order (a rank with none passes an empty batch).
+  // Reported to the trace hook as (the next step's sequence number, kTraceControl). Returns what
+  // Peek would have returned just before. A new limit waits one agreement, as for Set.
+  std::vector<PeekStatus> Adjust(const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits,
+                                 const std::vector<int32_t>& deltas, bool keep_cache = false);
+
   struct RoutedStats {
     uint64_t steps, empty_steps, rule_syncs, rules, held_calls;
   };
@@ -468,7 +482,8 @@ class HipRoutedRateLimitCache : public RateLimitCache {
   void run_control(int kind, std::deque<std::shared_ptr<PendingCall>>& ctl, uint64_t seq);
   std::vector<PeekStatus> peek_call(const RateLimitRequest& request,
                                     const std::vector<std::shared_ptr<RateLimit>>& limits, int kind,
-                                    const std::vector<PeekStatus>* values = nullptr, uint32_t keep = 0);
+                                    const std::vector<PeekStatus>* values = nullptr, uint32_t keep = 0,
+                                    const std::vector<int32_t>* deltas = nullptr);
   void fail(std::vector<std::shared_ptr<PendingCall>>& calls, const std::string& msg);
   void done_calls(size_t n);
 

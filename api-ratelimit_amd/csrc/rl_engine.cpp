@@ -97,14 +97,15 @@ enum KernelId {
   KT_FINGERPRINT, KT_HISTOGRAM, KT_HIST_SCAN, KT_SORT_PASS, KT_SCAN, KT_LEADER, KT_DECIDE, KT_FALLBACK, KT_MEMSET,
   KT_CAND, KT_V4_HIST, KT_V4_SCAN, KT_V4_PLACE, KT_V4_GROUP, KT_RESOLVE, KT_RULE_STATS, KT_CACHE_STATS, KT_CENSUS,
   KT_SET_INDEX, KT_SET_PLAN, KT_SET_APPLY, KT_SET_INDEX_ROUTED, KT_MERGE_PLAN, KT_MERGE_APPLY,
-  KT_ADJUST_INDEX, KT_ADJUST_APPLY, KT_COUNT
+  KT_ADJUST_INDEX, KT_ADJUST_APPLY, KT_ADJUST_INDEX_ROUTED, KT_ADJUST_PACK, KT_COUNT
 };
 const char* const kKernelNames[KT_COUNT] = {"k_fingerprint", "k_histogram", "k_hist_scan", "k_sort_pass", "k_scan",
                                             "k_leader",      "k_decide",    "fallback",    "memset",      "k_cand_state",
                                             "k4_hist",       "k4_scan",     "k4_place",    "k4_group",
                                             "k_resolve",     "k_rule_stats", "k_cache_stats", "k_census",
                                             "k_set_index",   "k_set_plan",  "k_set_apply", "k_set_index_routed",
-                                            "k_merge_plan",  "k_merge_apply", "k_adjust_index", "k_adjust_apply"};
+                                            "k_merge_plan",  "k_merge_apply", "k_adjust_index", "k_adjust_apply",
+                                            "k_adjust_index_routed", "k_adjust_pack"};
 
 enum Mode { MODE_LSD = 1, MODE_LSD_FULL = 2, MODE_V4 = 4 };
 
@@ -184,8 +185,16 @@ struct rl_engine {
   uint32_t set_plan_n = 0;
   SetScratch set_plan_sc{};
   uint32_t set_plan_gen[8] = {};
+  // a routed adjust's plan between rl_adjust_routed_plan and rl_adjust_routed_commit lives in the
+  // same scratch and is the same kind of open state (set_open with adj_plan): its index view and
+  // what its index pass counted
+  bool adj_plan = false;
+  AdjScratch adj_plan_sc{};
+  uint64_t adj_plan_absent = 0, adj_plan_applied = 0;
   int set_busy(const char* what) {
-    return set_open ? fail(RL_ESTATE, "%s while a routed set plan is open (call rl_set_routed_commit)", what) : 0;
+    if (!set_open) return 0;
+    return adj_plan ? fail(RL_ESTATE, "%s while a routed adjust plan is open (call rl_adjust_routed_commit)", what)
+                    : fail(RL_ESTATE, "%s while a routed set plan is open (call rl_set_routed_commit)", what);
   }
   // rl_merge's own scratch beside rl_set's index (rl_merge.h): the call's records on the device
   // (max_batch_desc of them) and the control block with its pinned copy, allocated at the first
@@ -1911,7 +1920,7 @@ int rl_reset(rl_engine* e) {
   if (e->n_fl) return e->fail(RL_ESTATE, "rl_reset while a batch is in flight");
   e->snap_close();
   e->restoring = false;
-  e->set_open = false;
+  e->set_open = e->adj_plan = false;
   return e->clear_table();
 }
 
@@ -2694,7 +2703,9 @@ int rl_set_routed_plan(rl_engine* e, const void* d_records, const rl_peek_reply*
   const char* what = "rl_set_routed_plan";
   if (e->n_fl) return e->fail(RL_ESTATE, "%s while a batch is in flight (call rl_wait)", what);
   if (e->restoring) return e->fail(RL_ESTATE, "%s between rl_restore_begin and rl_restore_end", what);
-  if (e->set_open) return e->fail(RL_ESTATE, "%s: a plan is open (call rl_set_routed_commit)", what);
+  if (e->set_open)
+    return e->fail(RL_ESTATE, "%s: a plan is open (call %s)", what,
+                   e->adj_plan ? "rl_adjust_routed_commit" : "rl_set_routed_commit");
   if (e->cfg.max_batch_desc > SET_MAX_DESC)
     return e->fail(RL_ECAPACITY, "%s: max_batch_desc %u above 2^29", what, e->cfg.max_batch_desc);
   if (n > e->cfg.max_batch_desc)
@@ -2747,6 +2758,8 @@ int rl_set_routed_plan(rl_engine* e, const void* d_records, const rl_peek_reply*
 int rl_set_routed_commit(rl_engine* e, int apply) {
   if (!e) return RL_EINVAL;
   if (!e->set_open) return e->fail(RL_ESTATE, "rl_set_routed_commit without an open plan (call rl_set_routed_plan)");
+  if (e->adj_plan)
+    return e->fail(RL_ESTATE, "rl_set_routed_commit: the open plan is a routed adjust's (call rl_adjust_routed_commit)");
   e->set_open = false;
   if (!apply || !e->set_plan_n) return 0;
   return set_apply(e, "rl_set_routed_commit", e->set_plan_n, e->set_plan_sc, e->set_plan_gen, nullptr, nullptr);
@@ -2809,7 +2822,7 @@ int rl_adjust(rl_engine* e, const rl_batch* b, const int32_t* delta, uint32_t fl
   he = hipGetLastError();
   if (he != hipSuccess) return e->hip_fail(he, "rl_adjust (nothing written)");
   const bool clear_cache = e->tab.local_cache && !(flags & RL_ADJUST_KEEP_CACHE);
-  e->timed(KT_ADJUST_APPLY, [&] { launch_adjust_apply(e->stream, clear_cache, sc); });
+  e->timed(KT_ADJUST_APPLY, [&] { launch_adjust_apply(e->stream, clear_cache, false, sc); });
   he = hipGetLastError();
   if (he == hipSuccess) he = hipMemcpyAsync(hc, sc.ctl, sizeof(AdjCtl), hipMemcpyDeviceToHost, e->stream);
   // the replies land in pinned memory first: a refused call leaves `out` as it was
@@ -2828,6 +2841,112 @@ int rl_adjust(rl_engine* e, const rl_batch* b, const int32_t* delta, uint32_t fl
   rep.floored = hc->w[ADJ_FLOORED][0];
   rep.capped = hc->w[ADJ_CAPPED][0];
   rep.unfrozen = hc->w[ADJ_UNFROZEN][0];
+  if (report) *report = rep;
+  return 0;
+}
+
+// Routed adjust, the engine's pieces (rl_hip.h "Routed adjust"). The plan is rl_adjust up to and
+// including k_adjust_index, over records that arrived from every origin; the commit is the rest.
+// Between the two the index and the control block stay in rl_set's scratch, which everything that
+// could touch it is refused from (set_busy).
+int rl_route_pack_adjust(rl_engine* e, const rl_batch* b, const uint32_t* d_perm, const int32_t* d_delta,
+                         uint32_t flags, void* d_send) {
+  if (!e || !b) return RL_EINVAL;
+  if (flags & ~(uint32_t)RL_ADJUST_KEEP_CACHE)
+    return e->fail(RL_EINVAL, "rl_route_pack_adjust: unknown flag bits 0x%x", flags);
+  if (b->n_desc && (!d_perm || !d_delta || !d_send || !b->rule_id))
+    return e->fail(RL_EINVAL, "rl_route_pack_adjust: null permutation, delta, rule id or record array");
+  if (!b->n_desc) return 0;
+  e->timed(KT_ADJUST_PACK, [&] {
+    launch_adjust_pack(e->stream, b->n_desc, RL_ROUTE_LOCAL, d_perm, b->rule_id, d_delta, flags & RL_ADJUST_KEEP_CACHE,
+                       reinterpret_cast<RRec*>(d_send));
+  });
+  const hipError_t he = hipGetLastError();
+  if (he != hipSuccess) return e->hip_fail(he, "rl_route_pack_adjust");
+  return 0;
+}
+
+int rl_adjust_routed_plan(rl_engine* e, const void* d_records, uint32_t n, rl_peek_reply* d_reply_or_null) {
+  if (!e) return RL_EINVAL;
+  const char* what = "rl_adjust_routed_plan";
+  if (e->n_fl) return e->fail(RL_ESTATE, "%s while a batch is in flight (call rl_wait)", what);
+  if (e->restoring) return e->fail(RL_ESTATE, "%s between rl_restore_begin and rl_restore_end", what);
+  if (e->set_open)
+    return e->fail(RL_ESTATE, "%s: a plan is open (call %s)", what,
+                   e->adj_plan ? "rl_adjust_routed_commit" : "rl_set_routed_commit");
+  if (e->cfg.max_batch_desc > SET_MAX_DESC)
+    return e->fail(RL_ECAPACITY, "%s: max_batch_desc %u above 2^29", what, e->cfg.max_batch_desc);
+  if (n > e->cfg.max_batch_desc)
+    return e->fail(RL_ECAPACITY, "%s: %u records exceed max_batch_desc %u", what, n, e->cfg.max_batch_desc);
+  if (n && !d_records) return e->fail(RL_EINVAL, "%s: null record array", what);
+  if (!e->d_rules) {
+    const int rc = rl_load_rules(e, nullptr, 0);
+    if (rc) return rc;
+  }
+  e->adj_plan_absent = e->adj_plan_applied = 0;
+  if (n) {
+    const int rc = e->set_ensure();
+    if (rc) return rc;
+    AdjScratch sc;
+    sc.index = reinterpret_cast<AdjEntry*>(e->set_sc.index);
+    sc.ctl = reinterpret_cast<AdjCtl*>(e->set_sc.ctl);
+    sc.log2_entries = 6;
+    while ((1ull << sc.log2_entries) < 2ull * n) ++sc.log2_entries;  // <= the allocation's: n <= max_batch_desc
+    const AdjCtl* hc = reinterpret_cast<const AdjCtl*>(e->h_set_ctl);
+    hipError_t he = hipMemsetAsync(sc.index, 0, sizeof(AdjEntry) << sc.log2_entries, e->stream);
+    if (he == hipSuccess) he = hipMemsetAsync(sc.ctl, 0, sizeof(AdjCtl), e->stream);
+    if (he == hipSuccess) {
+      e->timed(KT_ADJUST_INDEX_ROUTED, [&] {
+        launch_adjust_index_routed(e->stream, reinterpret_cast<const RRec*>(d_records), n, e->d_rules, e->n_rules,
+                                   e->tab, d_reply_or_null, sc);
+      });
+      he = hipGetLastError();
+    }
+    if (he == hipSuccess) he = hipMemcpyAsync(e->h_set_ctl, sc.ctl, sizeof(AdjCtl), hipMemcpyDeviceToHost, e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+    if (he != hipSuccess) return e->hip_fail(he, "rl_adjust_routed_plan (nothing written)");
+    if (e->timing) e->fold_marks();
+    const uint32_t err = hc->w[ADJ_ERR][0];
+    if (err & ADJ_ERR_BADREC)
+      return e->fail(RL_EINVAL, "%s: a record's rule id is unknown, its time is above 0xFFFD0000 or its rule word has "
+                                "bits above 16 set (nothing written)", what);
+    if (err) return e->fail(RL_EDEVICE, "%s: the call's index overflowed (nothing written)", what);
+    e->adj_plan_sc = sc;
+    e->adj_plan_absent = hc->w[ADJ_ABSENT][0];
+    e->adj_plan_applied = hc->w[ADJ_APPLIED][0];
+  }
+  e->set_open = e->adj_plan = true;
+  e->set_plan_n = n;
+  return 0;
+}
+
+int rl_adjust_routed_commit(rl_engine* e, int apply, rl_adjust_report* report) {
+  if (!e) return RL_EINVAL;
+  if (!e->set_open || !e->adj_plan)
+    return e->fail(RL_ESTATE, e->set_open ? "rl_adjust_routed_commit: the open plan is a routed set's (call "
+                                            "rl_set_routed_commit)"
+                                          : "rl_adjust_routed_commit without an open plan (call rl_adjust_routed_plan)");
+  e->set_open = e->adj_plan = false;
+  if (!apply) return 0;
+  rl_adjust_report rep;
+  memset(&rep, 0, sizeof rep);
+  rep.descriptors = e->set_plan_n;
+  rep.absent = e->adj_plan_absent;
+  rep.applied = e->adj_plan_applied;
+  if (e->set_plan_n) {
+    const AdjScratch& sc = e->adj_plan_sc;
+    const AdjCtl* hc = reinterpret_cast<const AdjCtl*>(e->h_set_ctl);
+    e->timed(KT_ADJUST_APPLY, [&] { launch_adjust_apply(e->stream, e->tab.local_cache != 0, true, sc); });
+    hipError_t he = hipGetLastError();
+    if (he == hipSuccess) he = hipMemcpyAsync(e->h_set_ctl, sc.ctl, sizeof(AdjCtl), hipMemcpyDeviceToHost, e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+    if (he != hipSuccess)
+      return e->hip_fail(he, "rl_adjust_routed_commit: applying pass (the table may hold part of the call)");
+    if (e->timing) e->fold_marks();
+    rep.floored = hc->w[ADJ_FLOORED][0];
+    rep.capped = hc->w[ADJ_CAPPED][0];
+    rep.unfrozen = hc->w[ADJ_UNFROZEN][0];
+  }
   if (report) *report = rep;
   return 0;
 }

@@ -54,6 +54,7 @@
 #include "rl_common.h"
 #include "rl_hip.h"
 #include "rl_internal.h"
+#include "rl_adjust.h"
 #include "rl_set.h"
 
 using namespace rlhip;
@@ -322,13 +323,23 @@ struct EmuXport : Xport {
   }
 };
 
-// The routed by-key calls (rl_router_peek / _forget / _set): one origin / exchange / owner /
-// reply sequence, differing in the owner's work (and, for a set, the values beside the records
-// and the plan-status exchange ahead of any write).
-enum ByKeyOp { OP_PEEK, OP_FORGET, OP_SET };
+// The routed by-key calls (rl_router_peek / _forget / _set / _adjust): one origin / exchange /
+// owner / reply sequence, differing in the owner's work (and, for a set, the values beside the
+// records; for a set and an adjust, the plan-status exchange ahead of any write).
+enum ByKeyOp { OP_PEEK, OP_FORGET, OP_SET, OP_ADJUST };
 const char* op_name(ByKeyOp op) {
-  return op == OP_SET ? "rl_router_set" : op == OP_FORGET ? "rl_router_forget" : "rl_router_peek";
+  return op == OP_ADJUST ? "rl_router_adjust"
+         : op == OP_SET  ? "rl_router_set"
+                         : op == OP_FORGET ? "rl_router_forget" : "rl_router_peek";
 }
+inline bool two_phase(ByKeyOp op) { return op == OP_SET || op == OP_ADJUST; }
+// What an adjust carries beside the batches: one delta array, one flags word and one report per
+// engine passed at create.
+struct AdjustArgs {
+  const int32_t* const* delta;
+  const uint32_t* flags;
+  rl_adjust_report* const* report;
+};
 
 // One owner run: consecutive origins' records (compact by origin) whose times fit one engine batch.
 struct Run {
@@ -431,6 +442,11 @@ struct Shard {
   rl_peek_reply* sv_d = nullptr;
   rl_peek_reply* sv_send = nullptr;
   rl_peek_reply* sv_recv = nullptr;
+  // routed adjust (allocated at its first call): the origin's deltas in descriptor order (pinned +
+  // device staging); the commit's report until the call is known to have succeeded
+  int32_t* ad_h = nullptr;
+  int32_t* ad_d = nullptr;
+  rl_adjust_report ad_rep{};
 };
 
 struct StepSlot {
@@ -550,7 +566,17 @@ struct rl_router {
   int peek_stage(uint32_t s, uint32_t k, const rl_batch& hb, rl_batch& db);
   int set_validate(const Shard& S, const rl_batch& b, const rl_peek_reply* values, std::string& why) const;
   int set_alloc(Shard& S);
-  int peek(const rl_batch* batches, rl_peek_reply* const* out, ByKeyOp op, const rl_peek_reply* const* values = nullptr);
+  int peek(const rl_batch* batches, rl_peek_reply* const* out, ByKeyOp op, const rl_peek_reply* const* values = nullptr,
+           const AdjustArgs* adj = nullptr);
+  int adjust_alloc(Shard& S);
+  // the owner's two phases of a set or an adjust
+  int owner_plan(Shard& S, ShardStep& t, ByKeyOp op) {
+    return op == OP_SET ? rl_set_routed_plan(S.e, t.recv, S.sv_recv, t.n_in, S.pk_reply)
+                        : rl_adjust_routed_plan(S.e, t.recv, t.n_in, S.pk_reply);
+  }
+  int owner_commit(Shard& S, ByKeyOp op, int apply) {
+    return op == OP_SET ? rl_set_routed_commit(S.e, apply) : rl_adjust_routed_commit(S.e, apply, &S.ad_rep);
+  }
   int peek_coll(uint32_t k, rl_peek_reply* const* out, ByKeyOp op);
   int peek_local(uint32_t k, rl_peek_reply* const* out, ByKeyOp op);
   void note_combine(uint32_t s, uint32_t k);
@@ -584,6 +610,8 @@ void rl_router::free_all() {
       if (p) (void)hipFree(p);
     if (s.pk_h_in) (void)hipHostFree(s.pk_h_in);
     if (s.sv_h) (void)hipHostFree(s.sv_h);
+    if (s.ad_d) (void)hipFree(s.ad_d);
+    if (s.ad_h) (void)hipHostFree(s.ad_h);
     if (s.d_hot) (void)hipFree(s.d_hot);
     if (s.h_hot) (void)hipHostFree(s.h_hot);
     if (s.ev_hot) (void)hipEventDestroy(s.ev_hot);
@@ -1651,9 +1679,19 @@ int rl_router::set_alloc(Shard& S) {
   return he == hipSuccess ? 0 : RL_EHIP;
 }
 
-// The origin half of every by-key call, then the transport's half. values: a set's, per engine.
+int rl_router::adjust_alloc(Shard& S) {
+  if (S.ad_h && S.ad_d) return 0;
+  const size_t d = (size_t)(cfg.max_desc ? cfg.max_desc : 1u) * sizeof(int32_t);
+  hipError_t he = hipSuccess;
+  if (!S.ad_h) he = hipHostMalloc(&S.ad_h, d, hipHostMallocDefault);
+  if (he == hipSuccess && !S.ad_d) he = hipMalloc(&S.ad_d, d);
+  return he == hipSuccess ? 0 : RL_EHIP;
+}
+
+// The origin half of every by-key call, then the transport's half. values: a set's, per engine;
+// adj: an adjust's deltas, flags and reports, per engine.
 int rl_router::peek(const rl_batch* batches, rl_peek_reply* const* out, ByKeyOp op,
-                    const rl_peek_reply* const* values) {
+                    const rl_peek_reply* const* values, const AdjustArgs* adj) {
   const char* what = op_name(op);
   if (broken) return fail(RL_ECOMM, "the router's communicator was aborted after a transport failure");
   if (done != seq) return fail(RL_ESTATE, "%s with a routed step in flight: call rl_router_wait", what);
@@ -1676,8 +1714,17 @@ int rl_router::peek(const rl_batch* batches, rl_peek_reply* const* out, ByKeyOp 
       t.msg = "null reply array";
     }
     if (!rc && op == OP_SET) rc = set_validate(S, batches[s], values[s], t.msg);
+    if (!rc && op == OP_ADJUST && batches[s].n_desc && !adj->delta[s]) {
+      rc = RL_EINVAL;
+      t.msg = "null delta array";
+    }
+    if (!rc && op == OP_ADJUST && (adj->flags[s] & ~(uint32_t)RL_ADJUST_KEEP_CACHE)) {
+      rc = RL_EINVAL;
+      t.msg = "unknown flag bits";
+    }
     if (!rc && (rc = peek_alloc(S))) t.msg = "reply buffer / staging allocation failed";
     if (!rc && op == OP_SET && (rc = set_alloc(S))) t.msg = "value buffer / staging allocation failed";
+    if (!rc && op == OP_ADJUST && (rc = adjust_alloc(S))) t.msg = "delta staging allocation failed";
     if (!rc && (rc = peek_stage(s, k, batches[s], t.b))) t.msg = "host staging copy failed";
     if (!rc && op == OP_SET && batches[s].n_desc) {
       const size_t nb = (size_t)batches[s].n_desc * sizeof(rl_peek_reply);
@@ -1687,16 +1734,33 @@ int rl_router::peek(const rl_batch* batches, rl_peek_reply* const* out, ByKeyOp 
         t.msg = "value staging copy failed";
       }
     }
+    if (!rc && op == OP_ADJUST && batches[s].n_desc) {
+      const size_t nb = (size_t)batches[s].n_desc * sizeof(int32_t);
+      memcpy(S.ad_h, adj->delta[s], nb);
+      if (hipMemcpyAsync(S.ad_d, S.ad_h, nb, hipMemcpyHostToDevice, S.os) != hipSuccess) {
+        rc = RL_EHIP;
+        t.msg = "delta staging copy failed";
+      }
+    }
     if (rc) t.b = rl_batch{};
     t.rc_pack = rc;
     pack(s, k, true);
+    if (op == OP_ADJUST && !t.rc_pack && t.b.n_desc) {  // the deltas and the keep bit into the records, behind the pack
+      launch_adjust_pack(S.os, t.b.n_desc, cfg.max_desc * cfg.n_shards, t.pb.perm, t.b.rule_id, S.ad_d,
+                         adj->flags[s] & RL_ADJUST_KEEP_CACHE, t.pb.send);
+      (void)hipGetLastError();  // (a failed launch shows at the stream's next wait)
+    }
     if (op == OP_SET && !t.rc_pack && t.b.n_desc) {  // the values to their records' places, behind the pack
       launch_set_values_pack(S.os, t.b.n_desc, cfg.max_desc * cfg.n_shards, t.pb.perm, S.sv_d, S.sv_send);
       (void)hipGetLastError();  // (a failed launch shows at the stream's next wait)
     }
     if (!coll) (void)hipStreamSynchronize(S.os);
   }
-  return coll ? peek_coll(k, out, op) : peek_local(k, out, op);
+  const int rc = coll ? peek_coll(k, out, op) : peek_local(k, out, op);
+  if (!rc && op == OP_ADJUST && adj->report)  // what each engine did as an owner
+    for (uint32_t s = 0; s < nl; ++s)
+      if (adj->report[s]) *adj->report[s] = sh[s].ad_rep;
+  return rc;
 }
 
 static const char* const kPackRefused =
@@ -1742,7 +1806,7 @@ int rl_router::peek_coll(uint32_t k, rl_peek_reply* const* out, ByKeyOp op) {
   if (bad >= 0) {  // every rank saw the same status words: all leave here, nothing looked up or written
     if (t.rc_pack) return fail(t.rc_pack, "%s: shard %u: %s", what, me, t.msg.c_str());
     return fail(RL_EPEER, "%s: shard %d refused its batch with %d: nothing was looked up or %s", what, bad,
-                (int)hr[XS * bad + 1], op == OP_SET ? "written" : "cleared");
+                (int)hr[XS * bad + 1], two_phase(op) ? "written" : "cleared");
   }
   size_t sc[MAXS], sd[MAXS], rc[MAXS], rd[MAXS];
   uint64_t ro = 0;
@@ -1772,13 +1836,13 @@ int rl_router::peek_coll(uint32_t k, rl_peek_reply* const* out, ByKeyOp op) {
   // owner: everything received, origin-major, on the engine stream behind the records
   int mine = 0;
   he = hipEventRecord(ev_rs, rs);
-  if (op == OP_SET) {
+  if (two_phase(op)) {
     // The plan synchronises the engine stream: the records' arrival is waited for here, bounded,
     // so that wait never stands behind a collective.
     if (he == hipSuccess)
-      if (int rcw = wait_bounded(ev_rs, nullptr, "all-to-all-v(set records)", &he)) return rcw;
+      if (int rcw = wait_bounded(ev_rs, nullptr, "all-to-all-v(set / adjust records)", &he)) return rcw;
     if (he == hipSuccess) {
-      mine = rl_set_routed_plan(S.e, t.recv, S.sv_recv, t.n_in, S.pk_reply);
+      mine = owner_plan(S, t, op);
       if (mine) t.msg = rl_last_error(S.e);
     } else {
       mine = RL_EHIP;
@@ -1791,19 +1855,19 @@ int rl_router::peek_coll(uint32_t k, rl_peek_reply* const* out, ByKeyOp op) {
     he = hipMemcpyAsync(t.d_x + 2 * XS * G, hw, 4 * G, hipMemcpyHostToDevice, rs);
     nr = xp->a2a(t.d_x + 2 * XS * G, t.d_x + 2 * XS * G + G, 4, rs);
     if (nr != ncclSuccess) {
-      if (!mine) (void)rl_set_routed_commit(S.e, 0);
-      return nccl_fail(nr, "all-to-all(set plan statuses)");
+      if (!mine) (void)owner_commit(S, op, 0);
+      return nccl_fail(nr, "all-to-all(plan statuses)");
     }
     if (he == hipSuccess) he = hipMemcpyAsync(hpl, t.d_x + 2 * XS * G + G, 4 * G, hipMemcpyDeviceToHost, rs);
     if (he == hipSuccess) he = hipEventRecord(ev_cnt, rs);
     if (he == hipSuccess) {
-      if (int rcw = wait_bounded(ev_cnt, nullptr, "all-to-all(set plan statuses)", &he)) {
-        if (!mine) (void)rl_set_routed_commit(S.e, 0);
+      if (int rcw = wait_bounded(ev_cnt, nullptr, "all-to-all(plan statuses)", &he)) {
+        if (!mine) (void)owner_commit(S, op, 0);
         return rcw;
       }
     }
     if (he != hipSuccess) {  // the peers' plan codes are unknown: nobody may write
-      if (!mine) (void)rl_set_routed_commit(S.e, 0);
+      if (!mine) (void)owner_commit(S, op, 0);
       abort_comm();
       return fail(RL_ECOMM, "%s: plan-status exchange: %s (communicator aborted)", what, hipGetErrorString(he));
     }
@@ -1811,12 +1875,12 @@ int rl_router::peek_coll(uint32_t k, rl_peek_reply* const* out, ByKeyOp op) {
     for (uint32_t j = 0; j < G && bad < 0; ++j)
       if (hpl[j]) bad = (int)j;
     if (bad >= 0) {  // every rank saw the same codes: no owner has written anything, out is untouched
-      if (!mine) (void)rl_set_routed_commit(S.e, 0);
+      if (!mine) (void)owner_commit(S, op, 0);
       if (mine) return fail(mine, "%s: shard %u (owner plan): %s", what, me, t.msg.c_str());
       return fail(RL_EPEER, "%s: owner %d refused its plan with %d: nothing was written anywhere", what, bad,
                   (int)hpl[bad]);
     }
-    mine = rl_set_routed_commit(S.e, 1);
+    mine = owner_commit(S, op, 1);
     if (mine) t.msg = rl_last_error(S.e);
   } else {
     if (he == hipSuccess) he = hipStreamWaitEvent(es, ev_rs, 0);
@@ -1872,11 +1936,11 @@ int rl_router::peek_coll(uint32_t k, rl_peek_reply* const* out, ByKeyOp op) {
     // after a failure to enqueue: drain the exchange stream (bounded), the statuses are lost
     if (int rcw = wait_bounded(nullptr, rs, "all-to-all(peek replies)", nullptr)) return rcw;
   }
-  if (mine) return fail(mine, "%s: shard %u (owner %s): %s", what, me, op == OP_SET ? "commit" : "lookup", t.msg.c_str());
+  if (mine) return fail(mine, "%s: shard %u (owner %s): %s", what, me, two_phase(op) ? "commit" : "lookup", t.msg.c_str());
   if (he != hipSuccess) return fail(RL_EHIP, "%s: reply exchange / unpack: %s", what, hipGetErrorString(he));
   for (uint32_t j = 0; j < G; ++j)
     if (hst[j])
-      return fail(RL_EPEER, "%s: owner %u failed its %s with %d", what, j, op == OP_SET ? "commit" : "lookup", (int)hst[j]);
+      return fail(RL_EPEER, "%s: owner %u failed its %s with %d", what, j, two_phase(op) ? "commit" : "lookup", (int)hst[j]);
   if (rc_un) return fail(rc_un, "%s: unpack: %s", what, rl_last_error(S.e));
   if (out && out[0] && t.b.n_desc) {
     he = hipMemcpy(out[0], d_out, (size_t)t.b.n_desc * sizeof(rl_peek_reply), hipMemcpyDeviceToHost);
@@ -1924,13 +1988,13 @@ int rl_router::peek_local(uint32_t k, rl_peek_reply* const* out, ByKeyOp op) {
   }
   if (he == hipSuccess) he = hipStreamSynchronize(rs);
   if (he != hipSuccess) return fail(RL_EHIP, "%s: record exchange: %s", what, hipGetErrorString(he));
-  if (op == OP_SET) {
+  if (two_phase(op)) {
     // every owner plans; the first failing shard's code ends the call with every plan dropped:
     // no owner has written anything
     int bad = -1, code = 0;
     for (uint32_t j = 0; j < G; ++j) {
       ShardStep& t = sh[j].st[k];
-      const int rc = rl_set_routed_plan(sh[j].e, t.recv, sh[j].sv_recv, t.n_in, sh[j].pk_reply);
+      const int rc = owner_plan(sh[j], t, op);
       t.rc_dec = rc;
       if (rc && bad < 0) {
         bad = (int)j;
@@ -1941,10 +2005,10 @@ int rl_router::peek_local(uint32_t k, rl_peek_reply* const* out, ByKeyOp op) {
     for (uint32_t j = 0; j < G; ++j) {
       ShardStep& t = sh[j].st[k];
       if (bad >= 0) {
-        if (!t.rc_dec) (void)rl_set_routed_commit(sh[j].e, 0);
+        if (!t.rc_dec) (void)owner_commit(sh[j], op, 0);
         continue;
       }
-      const int rc = rl_set_routed_commit(sh[j].e, 1);
+      const int rc = owner_commit(sh[j], op, 1);
       if (rc) return fail(rc, "%s: shard %u (owner commit): %s", what, j, rl_last_error(sh[j].e));
     }
     if (bad >= 0)
@@ -2003,6 +2067,13 @@ int rl_router_set(rl_router* r, const rl_batch* host_batches, const rl_peek_repl
                   rl_peek_reply* const* out_or_null) {
   if (!r || !host_batches || !values) return RL_EINVAL;
   return r->peek(host_batches, out_or_null, OP_SET, values);
+}
+
+int rl_router_adjust(rl_router* r, const rl_batch* host_batches, const int32_t* const* delta, const uint32_t* flags,
+                     rl_peek_reply* const* out_or_null, rl_adjust_report* const* report_or_null) {
+  if (!r || !host_batches || !delta || !flags) return RL_EINVAL;
+  const AdjustArgs a{delta, flags, report_or_null};
+  return r->peek(host_batches, out_or_null, OP_ADJUST, nullptr, &a);
 }
 
 int rl_router_unique_id(uint8_t* id_out) {

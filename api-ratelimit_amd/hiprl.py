@@ -319,6 +319,11 @@ ABI = [
     ("rl_set_routed_plan", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p], C.c_int),
     ("rl_set_routed_commit", [C.c_void_p, C.c_int], C.c_int),
     ("rl_router_set", [C.c_void_p, C.POINTER(RlBatch), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)], C.c_int),
+    ("rl_route_pack_adjust", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p], C.c_int),
+    ("rl_adjust_routed_plan", [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p], C.c_int),
+    ("rl_adjust_routed_commit", [C.c_void_p, C.c_int, C.POINTER(RlAdjustReport)], C.c_int),
+    ("rl_router_adjust", [C.c_void_p, C.POINTER(RlBatch), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32),
+                          C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)], C.c_int),
     ("rl_resize", [C.c_void_p, C.POINTER(C.c_uint32)], C.c_int),
     ("rl_rule_stats_add_device", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
     ("rl_rule_stats_read", [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32], C.c_int),
@@ -871,6 +876,35 @@ class Engine:
         does; else drop it."""
         self._check(self.lib.rl_set_routed_commit(self.h, int(bool(apply))), "rl_set_routed_commit")
 
+    def route_pack_adjust(self, n_desc: int, rule_ptr: int, perm_ptr: int, delta_ptr: int, send_ptr: int,
+                          keep_cache: bool = False):
+        """rl_route_pack_adjust: behind route_pack_strided of the same batch, descriptor i's delta
+        (int32 at delta_ptr) into its record's h word and rule_id[i] | keep_cache << 16 into its rule
+        word. All device memory, asynchronous on the engine stream."""
+        s = RlBatch()
+        s.n_desc, s.n_req, s.blob_bytes, s.reserved = n_desc, 0, 0, 0
+        s.rule_id = rule_ptr or None
+        self._check(self.lib.rl_route_pack_adjust(self.h, C.byref(s), perm_ptr or None, delta_ptr or None,
+                                                  ADJUST_KEEP_CACHE if keep_cache else 0, send_ptr or None),
+                    "rl_route_pack_adjust")
+
+    def adjust_routed_plan(self, rec_ptr: int, n: int, reply_ptr: int = 0):
+        """rl_adjust_routed_plan: phase 1 of a routed adjust over n routed records (ROUTE_RECORD_BYTES
+        each; h is the int32 delta, bit 16 of the rule word keep_cache) in device memory: the
+        replies (the state before the call) to reply_ptr when it is not 0, and the call's index.
+        Synchronous; on return a plan is open and nothing has been written, or RedisError and no plan
+        is open."""
+        self._check(self.lib.rl_adjust_routed_plan(self.h, rec_ptr or None, n, reply_ptr or None),
+                    "rl_adjust_routed_plan")
+
+    def adjust_routed_commit(self, apply: bool = True) -> dict:
+        """rl_adjust_routed_commit: phase 2. apply: the applying pass over the plan's index; else drop
+        it. Returns the report as a dict of ADJUST_REPORT_FIELDS (all 0 for a dropped plan)."""
+        rep = RlAdjustReport()
+        self._check(self.lib.rl_adjust_routed_commit(self.h, int(bool(apply)), C.byref(rep)),
+                    "rl_adjust_routed_commit")
+        return {f: int(getattr(rep, f)) for f in ADJUST_REPORT_FIELDS}
+
     def route_unpack_peek(self, n_desc: int, perm_ptr: int, back_ptr: int, out_ptr: int):
         """rl_route_unpack_peek: out[i] = back[perm[i]] (NIL where perm[i] is ROUTE_LOCAL), all in
         device memory, asynchronous on the engine stream."""
@@ -1321,6 +1355,40 @@ class Router:
         o = (C.c_void_p * self.n)(*[x.ctypes.data for x in outs]) if want_out else None
         self._check(self.lib.rl_router_set(self.h, arr, va, o), "rl_router_set")
         return [outs[i][:b.n_desc] for i, b in enumerate(batches)] if want_out else None
+
+    def adjust(self, batches, deltas, keep_cache=False, want_out: bool = True):
+        """rl_router_adjust: per engine passed at create a host Batch and its deltas (int32, one per
+        descriptor: Engine.adjust's), each correction applied at the owner of its key, summed per
+        (string, store) over every origin and clamped once; all owners or none. keep_cache: a bool,
+        or one bool per batch. Collective like peek / forget / set (an empty Batch where a rank
+        adjusts nothing). Returns (one PEEK_DTYPE array per batch, the state before the call, or
+        None; one report dict per engine: what it did as an owner)."""
+        keeps = [bool(keep_cache)] * self.n if isinstance(keep_cache, (bool, np.bool_)) else [bool(k) for k in keep_cache]
+        if len(keeps) != self.n or len(batches) != self.n or len(deltas) != self.n:
+            raise ValueError(f"rl_router_adjust: needs {self.n} batches, delta arrays and keep_cache flags")
+        ds = []
+        for b, delta in zip(batches, deltas):
+            d = np.asarray(delta)
+            if d.shape != (b.n_desc,):
+                raise ValueError(f"rl_router_adjust: {d.shape[0] if d.ndim == 1 else d.shape} deltas for "
+                                 f"{b.n_desc} descriptors")
+            if d.size and (d.dtype.kind not in "iu" or int(d.min()) < -2**31 or int(d.max()) > 2**31 - 1):
+                raise ValueError("rl_router_adjust: a delta is not an int32")
+            ds.append(np.ascontiguousarray(d, np.int32))
+        structs = [_batch_struct(b) for b in batches]
+        for s in structs:  # (ignored by the call; staged as zeros)
+            s.hits_addend, s.ttl_jitter = None, None
+        arr = (RlBatch * self.n)(*structs)
+        pads = [d if d.shape[0] else np.zeros(1, np.int32) for d in ds]
+        da = (C.c_void_p * self.n)(*[x.ctypes.data for x in pads])
+        fl = (C.c_uint32 * self.n)(*[ADJUST_KEEP_CACHE if k else 0 for k in keeps])
+        outs = [np.zeros(max(1, b.n_desc), PEEK_DTYPE) for b in batches]
+        o = (C.c_void_p * self.n)(*[x.ctypes.data for x in outs]) if want_out else None
+        reps = (RlAdjustReport * self.n)()
+        ra = (C.c_void_p * self.n)(*[C.addressof(reps[i]) for i in range(self.n)])
+        self._check(self.lib.rl_router_adjust(self.h, arr, da, fl, o, ra), "rl_router_adjust")
+        return ([outs[i][:b.n_desc] for i, b in enumerate(batches)] if want_out else None,
+                [{f: int(getattr(reps[i], f)) for f in ADJUST_REPORT_FIELDS} for i in range(self.n)])
 
     def allgather_host(self, data: bytes, n_ranks: int) -> list:
         """rl_router_allgather_host: every rank's `data` (the same length everywhere), in rank

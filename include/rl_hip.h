@@ -913,8 +913,8 @@ int rl_set(rl_engine* e, const rl_batch* host_batch, const rl_peek_reply* values
  * fell below 0 / rose above 0xFFFFFFFF and stopped there (a sum of exactly 0 is not floored).
  *
  * Refused before anything changes (table, out and *report untouched):
- *   RL_ESTATE     a batch in flight, a restore open, or a routed-set plan open (an open snapshot
- *                 does not block the call)
+ *   RL_ESTATE     a batch in flight, a restore open, or a routed set or adjust plan open (an open
+ *                 snapshot does not block the call)
  *   RL_ECAPACITY  rl_peek's capacity limits, or max_batch_desc above 2^29
  *   RL_EINVAL     everything rl_peek refuses; delta == NULL with n_desc > 0; any flag bit other than
  *                 RL_ADJUST_KEEP_CACHE
@@ -928,8 +928,9 @@ int rl_set(rl_engine* e, const rl_batch* host_batch, const rl_peek_reply* values
  * other, and an open routed-set plan, which lives there, refuses this one. The batch goes through
  * rl_peek's free host staging slot; the replies pass through 16 B x max_batch_desc of pinned memory,
  * allocated at the first call that asks for them.
- * Out of scope: a router-level call, an engine-level form over routed records, a device-memory
- * form, adjusting while batches are in flight, a compact wire form. */
+ * The routed forms (rl_router_adjust; rl_adjust_routed_plan / _commit over routed records) are
+ * "Routed adjust" below. Out of scope: a device-memory form, adjusting while batches are in flight,
+ * a compact wire form. */
 enum { RL_ADJUST_KEEP_CACHE = 1u };
 typedef struct rl_adjust_report {   /* 64 B */
   uint64_t descriptors;  /* n_desc of the call */
@@ -1023,7 +1024,8 @@ int rl_router_forget(rl_router* r, const rl_batch* host_batches, rl_peek_reply* 
  *   RL_EHIP
  * n == 0 opens an empty plan whose commit does nothing (a rank that receives nothing keeps the
  * collective sequence). While a plan is open every entry point that an open restore refuses
- * returns RL_ESTATE; rl_reset and rl_destroy close the plan.
+ * returns RL_ESTATE (rl_adjust_routed_plan and rl_adjust_routed_commit too); rl_reset and rl_destroy
+ * close the plan.
  * rl_set_routed_commit: phase 2. apply != 0 runs rl_set's applying pass and publishes the occupancy
  * exactly as rl_set does (and fails as it does); apply == 0 drops the plan. RL_ESTATE with no plan
  * open. Either way the plan is closed.
@@ -1057,6 +1059,93 @@ int rl_set_routed_plan(rl_engine* e, const void* d_records, const rl_peek_reply*
 int rl_set_routed_commit(rl_engine* e, int apply);
 int rl_router_set(rl_router* r, const rl_batch* host_batches, const rl_peek_reply* const* values,
                   rl_peek_reply* const* out_or_null);
+
+/* ---- Routed adjust -----------------------------------------------------------
+ * rl_adjust where the keys are spread over the shards of a router. In a routed deployment an engine
+ * holds only the keys it owns, and the rank that learns that a request failed downstream is in
+ * general not the owner of that request's keys: this is the call that gives a charge back there.
+ * A routed forget or set is idempotent; an adjust is not (a refund applied twice is a double
+ * refund), and an owner can refuse after the records have moved (its max_batch_desc below what it
+ * received, a restore or plan open, a batch in flight). So the call is all owners or none, two-phase
+ * like rl_router_set. The plan is k_adjust_index's record form, which writes nothing to the table;
+ * the commit is k_adjust_apply, which does all the writing.
+ *
+ * Engine level (device memory):
+ * rl_route_pack_adjust: the origin's second pack step, behind rl_route_pack_strided of the same
+ * batch (d_perm and d_send as that call wrote them, no combining). For every descriptor i with
+ * d_perm[i] != RL_ROUTE_LOCAL the record d_send[d_perm[i]] gets h = (uint32_t)d_delta[i] and
+ * rule = rule_id[i] | (flags & RL_ADJUST_KEEP_CACHE) << 16 (rule ids are below 0xFFFF, the routed
+ * record's rule). Both are whole 32-bit stores computed from the batch; the record is not read and
+ * nothing else of the send buffer is touched. Ordered on the engine stream, returns at once. Reads
+ * n_desc and rule_id of the batch. RL_EINVAL for a null array with n_desc > 0 or a flag bit other
+ * than RL_ADJUST_KEEP_CACHE. With this the records alone carry the call: there is no second value
+ * exchange as a set has.
+ * rl_adjust_routed_plan: phase 1 over n such records. Identity and lookup are rl_peek_routed's (the
+ * record's prefix lanes, time and rule), then rl_adjust's own index step: a found record adds
+ * (int32_t)h, its rule's limit and one to its (string, store) pair's entry of the call's scratch
+ * index, and the entry collects "some found record of this pair came without KEEP_CACHE". Replies
+ * (rl_peek's, the state before the call, for every duplicate) go to d_reply when it is not NULL.
+ * A record is malformed when its rule id is not below the loaded rule count, its time is above
+ * 0xFFFD0000 or bits 17..31 of its rule word are not 0: it gets RL_PEEK_BAD and is never indexed.
+ * The call synchronises the engine stream. 0: a plan is open and nothing has been written. Any
+ * other return: nothing written and no plan open:
+ *   RL_ESTATE     a batch in flight, a restore open, or a set or adjust plan open
+ *   RL_ECAPACITY  n above max_batch_desc, or max_batch_desc above 2^29
+ *   RL_EINVAL     null records with n > 0; a malformed record (found on the device: the owner's
+ *                 host never sees the records)
+ *   RL_EDEVICE    the scratch index had no entry left (unreachable, as in rl_adjust)
+ *   RL_EHIP
+ * n == 0 opens an empty plan. The plan lives in rl_set's scratch, as rl_adjust's index does. While
+ * an adjust plan is open everything an open routed-set plan refuses returns RL_ESTATE, and so does
+ * the commit of the other kind (rl_set_routed_commit on an adjust plan, rl_adjust_routed_commit on a
+ * set plan: the plan stays open); rl_reset and rl_destroy close the plan.
+ * rl_adjust_routed_commit: phase 2. apply == 0 drops the plan. Otherwise rl_adjust's applying pass
+ * runs over the index: new = clamp(count + net, 0, 0xFFFFFFFF) once per pair; a pair's cache part
+ * runs when the local cache is on, net < 0, new <= the pair's smallest limit and at least one of the
+ * pair's found records came without KEEP_CACHE — with one flag on every record, rl_adjust's rule
+ * word for word. *report is filled as rl_adjust fills it, with descriptors = n, nil = 0 and
+ * descriptors == absent + applied (apply == 0 leaves it alone). RL_ESTATE with no adjust plan
+ * open. Either way the plan is closed. RL_EHIP from the applying pass: the table may hold part of
+ * the call, as rl_adjust documents.
+ *
+ * rl_router_adjust: rl_router_set's contract. Collective; one batch, one delta array, one flags
+ * word, one output (or NULL) and one report (or NULL) per engine passed at create; the two pointer
+ * arrays themselves may be NULL; host memory, synchronous; a rank with nothing to adjust passes
+ * n_desc == 0; RL_ESTATE before any collective while a step is in flight.
+ *   1. Origin: rl_router_peek's refusals, plus RL_EINVAL for a null delta array with n_desc > 0 or
+ *      a flag bit other than RL_ADJUST_KEEP_CACHE. The deltas are staged (4 B x max_desc of pinned
+ *      plus device memory, allocated at the first call), the batch is packed by owner (one record
+ *      per descriptor) and the deltas and the keep bit are written into the records behind it. A
+ *      refusal travels as this origin's status in the counts exchange: nothing is planned anywhere,
+ *      the failing rank returns its code (local transport: the first failing shard's) and the
+ *      others RL_EPEER.
+ *   2. Counts, then records: one all-to-all-v. No values travel.
+ *   3. Every owner runs rl_adjust_routed_plan over everything it received.
+ *   4. Each owner's plan code goes to every rank. If any is non-zero every owner drops its plan:
+ *      the failing rank returns its code and the others RL_EPEER (local transport: the first failing
+ *      shard's code). No owner has written anything; out and the reports are untouched.
+ *   5. Every owner commits; the replies and the commit status return by the reverse exchange and
+ *      the origin unpacks them into out. A HIP or communicator failure in this phase leaves
+ *      per-owner atomicity, as a routed set documents.
+ * Semantics: the deltas of one (string, store) pair are summed over all descriptors of all origins
+ * and applied once, clamped, so the result does not depend on the order of the origins: a counter
+ * of 5 given -10 by origin 0 and +3 by origin 1 ends at 0. out[s][i] is the state before the call,
+ * for every duplicate across descriptors and origins. *report[s] is what engine s did as an owner:
+ * its commit's report over the records it received; summed over the ranks these are the call's
+ * totals. Nil descriptors never leave their origin: an origin counts them from its replies
+ * (RL_PEEK_NIL), and it learns whether its own corrections were applied from RL_PEEK_FOUND in out.
+ * The call does not move the step clock, cannot return RL_ELATE, does not touch the hot sets and
+ * leaves rl_router_stats alone. An engine's max_batch_desc bounds what one owner can receive in one
+ * call (RL_ECAPACITY from its plan, so nobody applies).
+ * Out of scope: an adjust while steps are in flight, a device-memory form of the router call, a
+ * compact wire form, corrections to rule stats. */
+int rl_route_pack_adjust(rl_engine* e, const rl_batch* device_batch, const uint32_t* d_perm, const int32_t* d_delta,
+                         uint32_t flags, void* d_send);
+int rl_adjust_routed_plan(rl_engine* e, const void* d_records, uint32_t n, rl_peek_reply* d_reply_or_null);
+int rl_adjust_routed_commit(rl_engine* e, int apply, rl_adjust_report* report_or_null);
+int rl_router_adjust(rl_router* r, const rl_batch* host_batches, const int32_t* const* delta,
+                     const uint32_t* flags /* one per engine passed at create */,
+                     rl_peek_reply* const* out_or_null, rl_adjust_report* const* report_or_null);
 
 /* ---- Rule stats: per-rule stat counters summed on the device ---------------
  * The reference keeps four counters per limit, <FullKey>.total_hits / .over_limit / .near_limit /
