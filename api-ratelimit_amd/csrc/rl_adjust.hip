@@ -20,10 +20,10 @@
 namespace rlhip {
 namespace adjust {
 
-// The loads go out as k_peek's do (rl_peek.hip): (offsets, rule id, request index, the delta),
-// then (now, the rule entry, the prefix's first 32 bytes), every one unconditional at a clamped
-// index. A thread past n_desc reads descriptor n_desc - 1 and uses nothing of it: it stays for the
-// block's sums.
+// The loads go out as rl_peek.h's desc_front sends them, with the delta beside the first level.
+// The front is written out here: through desc_front the kernel compiled to another load order and
+// measured 1 % slower ("By-key refactor"). A thread past n_desc reads descriptor
+// n_desc - 1 and uses nothing of it (`live`): it stays for the block's sums.
 __global__ __launch_bounds__(NT) void k_adjust_index(const DevBatch in, const DevRule* __restrict__ rules,
                                                      const uint32_t n_rules, const uint64_t seed, const TableDesc tab,
                                                      const int32_t* __restrict__ delta, rl_peek_reply* __restrict__ out,

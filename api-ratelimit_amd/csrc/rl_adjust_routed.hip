@@ -19,17 +19,15 @@ namespace adjust {
 
 constexpr uint32_t RREC_KEEP = 1u << 16;  // rule word: this record's RL_ADJUST_KEEP_CACHE
 
-// k_peek_routed's three dependent levels, each one run of loads waited for once: the record
-// (32 B), then the rule entry at a clamped id, then the key's first table slot (peek_key_slot,
-// inside adjust_key); then adjust_key's index probe. The identity comes from the record as
-// k_peek_routed takes it: no prefix hashing, no blob.
+// k_peek_routed's three dependent levels, each one run of loads waited for once: rl_peek.h's
+// rec_front with the keep word (the record, then the rule entry), then the key's first table slot
+// (peek_key_slot, inside adjust_key); then adjust_key's index probe.
 //
 // The owner's host never sees the records, so what rl_adjust checks on the host is checked here:
-// a record whose rule id is not below n_rules, whose time is above MAX_NOW or whose rule word has
-// a bit above the keep bit set is malformed: it gets RL_PEEK_BAD, sets ADJ_ERR_BADREC and indexes
-// nothing (the rule table holds >= 1 entry, host-checked). A thread past n reads record n - 1 and
-// uses nothing of it: it stays for the block's sums. No lane waits for another; the loops are the
-// probe (bounded by the region size) and the insert (bounded by the index size).
+// a record that is not ok gets RL_PEEK_BAD, sets ADJ_ERR_BADREC and indexes nothing. A thread past
+// n reads record n - 1 and uses nothing of it: it stays for the block's sums. No lane waits for
+// another; the loops are the probe (bounded by the region size) and the insert (bounded by the
+// index size).
 __global__ __launch_bounds__(NT) void k_adjust_index_routed(const RRec* __restrict__ recs, const uint32_t n,
                                                             const DevRule* __restrict__ rules, const uint32_t n_rules,
                                                             const TableDesc tab, rl_peek_reply* __restrict__ out,
@@ -37,20 +35,14 @@ __global__ __launch_bounds__(NT) void k_adjust_index_routed(const RRec* __restri
   const uint32_t gi = blockIdx.x * NT + threadIdx.x;
   const bool live = gi < n;
   const uint32_t i = live ? gi : n - 1u;  // n >= 1: the launch is skipped for an empty call
-  const RRec rc = recs[i];
-  const uint32_t rl = rc.rule & 0xFFFFu;
-  const bool rule_ok = !(rc.rule >> 17) && rl < n_rules;
-  const DevRule rr = rules[rule_ok ? rl : 0u];  // never indexed with a bad id
-  const bool ok = live && rule_ok && (int64_t)rc.now <= MAX_NOW;
-  // One use of the record's lanes and the rule entry ahead of the branch on `ok` (k_peek_routed):
-  // without it the compiler loads only the record's upper half first and fetches the lanes behind
-  // the branch, a round trip of their own.
-  asm volatile("" ::"v"(rc.a), "v"(rc.b), "v"(rr.unit), "v"(rr.div));
+  const peek::RecFront f = peek::rec_front(recs, rules, n_rules, i, live, true);
+  const RRec& rc = f.rc;
+  const bool ok = f.ok;
   rl_peek_reply rep;
   rep.count = rep.ttl_s = rep.cached_s = 0u;
   rep.flags = RL_PEEK_BAD;
   bool applied = false;
-  if (ok) applied = adjust_key<true>(FpState{rc.a, rc.b}, rc.now, rr, (int32_t)rc.h, !(rc.rule & RREC_KEEP), tab, sc, rep);
+  if (ok) applied = adjust_key<true>(FpState{rc.a, rc.b}, rc.now, f.rr, (int32_t)rc.h, !(rc.rule & RREC_KEEP), tab, sc, rep);
   if (live && out) out[i] = rep;
   if (live && !ok) atomicOr(&sc.ctl->w[ADJ_ERR][0], ADJ_ERR_BADREC);
   block_add3(false, ok && !applied, applied, ADJ_NIL, ADJ_ABSENT, ADJ_APPLIED, sc.ctl);

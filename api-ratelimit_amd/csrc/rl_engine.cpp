@@ -25,6 +25,7 @@
 #include "rl_hip.h"
 #include "rl_internal.h"
 #include "rl_merge.h"
+#include "rl_peek.h"
 #include "rl_resolve.h"
 #include "rl_set.h"
 #include "rl_snapshot.h"
@@ -80,11 +81,6 @@ void launch_v4_group(hipStream_t st, const rl_batch& b, const DevRule* rules, ui
                      int cand_on, uint64_t seed, void* scratch, int routed, RegionOcc* occ, EngineCtl* ctl,
                      EngineCtl* next_ctl, EngineCtl* hctl, HotCand* hcand, const MRec* srec,
                      const uint16_t* tstart);
-void launch_peek(hipStream_t, const rl_batch&, const DevRule*, uint32_t, uint64_t, const TableDesc&, rl_peek_reply*,
-                 bool forget);
-void launch_peek_routed(hipStream_t, const RRec*, uint32_t, const DevRule*, uint32_t, const TableDesc&, rl_peek_reply*,
-                        bool forget);
-void launch_peek_unpack(hipStream_t, uint32_t, const uint32_t*, const rl_peek_reply*, rl_peek_reply*);
 void launch_rule_stats(hipStream_t, const rl_batch&, const rl_status*, uint32_t, rl_rule_stat*, const EngineCtl*, int,
                        uint32_t);
 }  // namespace rlhip
@@ -110,6 +106,18 @@ const char* const kKernelNames[KT_COUNT] = {"k_fingerprint", "k_histogram", "k_h
 enum Mode { MODE_LSD = 1, MODE_LSD_FULL = 2, MODE_V4 = 4 };
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// log2 of the entries of a by-key call's scratch index: the first power of two >= 2 n, 64 at the
+// least. Grows with n, so a call's is never above the allocation's (n <= max_batch_desc).
+uint32_t index_log2(uint64_t n) {
+  uint32_t lg = 6;
+  while ((1ull << lg) < 2 * n) ++lg;
+  return lg;
+}
+// what a stream failure says after the call's name: before anything was written, and behind an
+// applying pass (set's, adjust's, merge's)
+const char kNothingWritten[] = " (nothing written)";
+const char kApplyFailed[] = ": applying pass (the table may hold part of the call)";
 
 // Wait for an event by polling. A blocking wait wakes the submitter thread ≈20 µs after the
 // GPU signals, and with two batches in flight that delay lands directly on the next batch's
@@ -178,23 +186,59 @@ struct rl_engine {
   // their own (16 B x max_batch_desc, allocated at the first call that asks for them and kept), so
   // that a refused call leaves the caller's array alone
   rl_peek_reply* h_adj_rep = nullptr;
-  // a routed set's plan between rl_set_routed_plan and rl_set_routed_commit: its records, its
-  // scratch view, its window generation per region. While it is open the engine refuses what an
-  // open restore refuses (set_busy).
-  bool set_open = false;
-  uint32_t set_plan_n = 0;
-  SetScratch set_plan_sc{};
-  uint32_t set_plan_gen[8] = {};
-  // a routed adjust's plan between rl_adjust_routed_plan and rl_adjust_routed_commit lives in the
-  // same scratch and is the same kind of open state (set_open with adj_plan): its index view and
-  // what its index pass counted
-  bool adj_plan = false;
-  AdjScratch adj_plan_sc{};
-  uint64_t adj_plan_absent = 0, adj_plan_applied = 0;
-  int set_busy(const char* what) {
-    if (!set_open) return 0;
-    return adj_plan ? fail(RL_ESTATE, "%s while a routed adjust plan is open (call rl_adjust_routed_commit)", what)
-                    : fail(RL_ESTATE, "%s while a routed set plan is open (call rl_set_routed_commit)", what);
+  // rl_adjust's view of rl_set's scratch for a call of n descriptors
+  AdjScratch adj_view(uint32_t n) const {
+    return AdjScratch{reinterpret_cast<AdjEntry*>(set_sc.index), index_log2(n), reinterpret_cast<AdjCtl*>(set_sc.ctl)};
+  }
+  // The plan between rl_set_routed_plan / rl_adjust_routed_plan and its commit. Its index and its
+  // control block stay in rl_set's scratch, so while one is open the engine refuses what an open
+  // restore refuses (quiet, set_busy).
+  struct Plan {
+    enum Kind { NONE, SET, ADJUST } kind = NONE;
+    uint32_t n = 0;             // records
+    SetScratch set_sc{};        // a set's scratch view
+    uint32_t set_gen[8] = {};   // ... and its window generation per region
+    AdjScratch adj_sc{};        // an adjust's index view (its counts wait in the control block)
+    static const char* form(Kind k) { return k == ADJUST ? "adjust" : "set"; }
+  } plan;
+  // refuses `what` while a plan is open (planning: in the words of the two plan entry points)
+  int set_busy(const char* what, bool planning = false) {
+    if (plan.kind == Plan::NONE) return 0;
+    const char* form = Plan::form(plan.kind);
+    if (planning) return fail(RL_ESTATE, "%s: a plan is open (call rl_%s_routed_commit)", what, form);
+    return fail(RL_ESTATE, "%s while a routed %s plan is open (call rl_%s_routed_commit)", what, form, form);
+  }
+  // The gate in front of every call that needs the engine quiet: nothing in flight, no restore and
+  // no plan open. restore_text: the caller's own words for an open restore (rl_restore_begin's).
+  int quiet(const char* what, bool planning = false, const char* restore_text = nullptr) {
+    if (n_fl) return fail(RL_ESTATE, "%s while a batch is in flight (call rl_wait)", what);
+    if (restoring && restore_text) return fail(RL_ESTATE, "%s", restore_text);
+    if (restoring) return fail(RL_ESTATE, "%s between rl_restore_begin and rl_restore_end", what);
+    return set_busy(what, planning);
+  }
+  // A commit of form k takes the open plan, which must be of its form, and closes it.
+  int plan_take(Plan::Kind k) {
+    const char* form = Plan::form(k);
+    if (plan.kind == Plan::NONE)
+      return fail(RL_ESTATE, "rl_%s_routed_commit without an open plan (call rl_%s_routed_plan)", form, form);
+    if (plan.kind != k)
+      return fail(RL_ESTATE, "rl_%s_routed_commit: the open plan is a routed %s's (call rl_%s_routed_commit)", form,
+                  Plan::form(plan.kind), Plan::form(plan.kind));
+    plan.kind = Plan::NONE;
+    return 0;
+  }
+  // Behind a call's last launch: its control block into the pinned copy h_ctl, n replies from d_rep
+  // to `out` (unless null), one stream synchronise. A failure's text is `what` with `tail`.
+  int fetch_ctl(void* h_ctl, const void* d_ctl, size_t bytes, const char* what, const char* tail,
+                rl_peek_reply* out = nullptr, const rl_peek_reply* d_rep = nullptr, uint32_t n = 0) {
+    hipError_t he = hipGetLastError();
+    if (he == hipSuccess) he = hipMemcpyAsync(h_ctl, d_ctl, bytes, hipMemcpyDeviceToHost, stream);
+    if (he == hipSuccess && out)
+      he = hipMemcpyAsync(out, d_rep, (size_t)n * sizeof(rl_peek_reply), hipMemcpyDeviceToHost, stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    if (he != hipSuccess) return hip_fail(he, (std::string(what) + tail).c_str());
+    if (timing) fold_marks();
+    return 0;
   }
   // rl_merge's own scratch beside rl_set's index (rl_merge.h): the call's records on the device
   // (max_batch_desc of them) and the control block with its pinned copy, allocated at the first
@@ -453,6 +497,17 @@ struct rl_engine {
     f();
     hipEventRecord(b, stream);
     marks.push_back({kid, a, b});
+  }
+
+  // The first half of every adjust: zero the call's index and control block and queue `index` (the
+  // form's index kernel, timed under kt). No synchronise.
+  template <class F>
+  hipError_t adjust_index_run(const AdjScratch& sc, int kt, F index) {
+    hipError_t he = hipMemsetAsync(sc.index, 0, sizeof(AdjEntry) << sc.log2_entries, stream);
+    if (he == hipSuccess) he = hipMemsetAsync(sc.ctl, 0, sizeof(AdjCtl), stream);
+    if (he != hipSuccess) return he;
+    timed(kt, index);
+    return hipGetLastError();
   }
 
   // the finished event pairs into the per-kernel totals (the stream is synchronised)
@@ -1920,7 +1975,7 @@ int rl_reset(rl_engine* e) {
   if (e->n_fl) return e->fail(RL_ESTATE, "rl_reset while a batch is in flight");
   e->snap_close();
   e->restoring = false;
-  e->set_open = e->adj_plan = false;
+  e->plan.kind = rl_engine::Plan::NONE;
   return e->clear_table();
 }
 
@@ -1956,9 +2011,7 @@ static uint32_t snap_flags(const rl_engine* e) {
 
 int rl_snapshot_begin(rl_engine* e, rl_snapshot_header* out) {
   if (!e || !out) return RL_EINVAL;
-  if (e->n_fl) return e->fail(RL_ESTATE, "rl_snapshot_begin while a batch is in flight (call rl_wait)");
-  if (e->restoring) return e->fail(RL_ESTATE, "rl_snapshot_begin between rl_restore_begin and rl_restore_end");
-  if (int rc = e->set_busy("rl_snapshot_begin")) return rc;
+  if (int rc = e->quiet("rl_snapshot_begin")) return rc;
   if (e->snap_open) return e->fail(RL_ESTATE, "a snapshot is open (call rl_snapshot_end)");
   int rc = e->snap_alloc();
   if (rc) return rc;
@@ -2066,9 +2119,7 @@ static int snap_header_check(rl_engine* e, const rl_snapshot_header* h, uint32_t
 
 int rl_restore_begin(rl_engine* e, const rl_snapshot_header* h) {
   if (!e || !h) return RL_EINVAL;
-  if (e->n_fl) return e->fail(RL_ESTATE, "rl_restore_begin while a batch is in flight (call rl_wait)");
-  if (e->restoring) return e->fail(RL_ESTATE, "a restore is open (call rl_restore_end)");
-  if (int rc = e->set_busy("rl_restore_begin")) return rc;
+  if (int rc = e->quiet("rl_restore_begin", false, "a restore is open (call rl_restore_end)")) return rc;
   if (int rc = snap_header_check(e, h, RL_SNAP_SPLIT | RL_SNAP_LAG,
                                  "snapshot per_second_split / lag window setting differs from this engine's"))
     return rc;
@@ -2206,9 +2257,7 @@ int rl_engine::merge_ensure() {
 int rl_merge(rl_engine* e, const rl_snapshot_header* h, const void* host_recs, uint32_t n, int64_t now,
              rl_merge_report* report) {
   if (!e || !h) return RL_EINVAL;
-  if (e->n_fl) return e->fail(RL_ESTATE, "rl_merge while a batch is in flight (call rl_wait)");
-  if (e->restoring) return e->fail(RL_ESTATE, "rl_merge between rl_restore_begin and rl_restore_end");
-  if (int rc = e->set_busy("rl_merge")) return rc;
+  if (int rc = e->quiet("rl_merge")) return rc;
   if (e->cfg.max_batch_desc > SET_MAX_DESC)
     return e->fail(RL_ECAPACITY, "rl_merge: max_batch_desc %u above 2^29", e->cfg.max_batch_desc);
   if (n > e->cfg.max_batch_desc)
@@ -2262,21 +2311,15 @@ int rl_merge(rl_engine* e, const rl_snapshot_header* h, const void* host_recs, u
   a.now = t;
   a.T = T;
   a.index = e->set_sc.index;
-  a.log2_entries = 6;
-  while ((1ull << a.log2_entries) < 2ull * n) ++a.log2_entries;  // <= the allocation's: n <= max_batch_desc
+  a.log2_entries = index_log2(n);
   a.desc = e->set_sc.desc;
   a.ctl = e->d_merge_ctl;
   MergeCtl* hc = e->h_merge_ctl;
   if (he == hipSuccess) he = hipMemsetAsync(a.index, 0, sizeof(SetEntry) << a.log2_entries, e->stream);
   if (he == hipSuccess) he = hipMemsetAsync(a.ctl, 0, sizeof(MergeCtl), e->stream);
-  if (he == hipSuccess) {
-    e->timed(KT_MERGE_PLAN, [&] { launch_merge_plan(e->stream, e->tab, a); });
-    he = hipGetLastError();
-  }
-  if (he == hipSuccess) he = hipMemcpyAsync(hc, a.ctl, sizeof(MergeCtl), hipMemcpyDeviceToHost, e->stream);
-  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
   if (he != hipSuccess) return e->hip_fail(he, "rl_merge (nothing written)");
-  if (e->timing) e->fold_marks();
+  e->timed(KT_MERGE_PLAN, [&] { launch_merge_plan(e->stream, e->tab, a); });
+  if ((rc = e->fetch_ctl(hc, a.ctl, sizeof(MergeCtl), "rl_merge", kNothingWritten)) != 0) return rc;
   if (hc->err & MERGE_ERR_DUP)
     return e->fail(RL_EINVAL, "rl_merge: one identity (claim word, key) occurs twice in the call (nothing written)");
   if (hc->err & MERGE_ERR_MIXED)
@@ -2295,11 +2338,7 @@ int rl_merge(rl_engine* e, const rl_snapshot_header* h, const void* host_recs, u
   rep.dropped_over = hc->over[0];
   rep.dropped_empty = hc->empty[0];
   e->timed(KT_MERGE_APPLY, [&] { launch_merge_apply(e->stream, e->tab, a); });
-  he = hipGetLastError();
-  if (he == hipSuccess) he = hipMemcpyAsync(hc, a.ctl, sizeof(MergeCtl), hipMemcpyDeviceToHost, e->stream);
-  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-  if (he != hipSuccess) return e->hip_fail(he, "rl_merge: applying pass (the table may hold part of the call)");
-  if (e->timing) e->fold_marks();
+  if ((rc = e->fetch_ctl(hc, a.ctl, sizeof(MergeCtl), "rl_merge", kApplyFailed)) != 0) return rc;
   if (hc->err)
     return e->fail(RL_EDEVICE, "rl_merge: a region had no free slot left (the table may hold part of the call)");
   RegionOcc nocc[8];
@@ -2335,9 +2374,7 @@ int rl_merge(rl_engine* e, const rl_snapshot_header* h, const void* host_recs, u
 // prefixes and stay.
 int rl_resize(rl_engine* e, const uint32_t log2_slots[4]) {
   if (!e || !log2_slots) return RL_EINVAL;
-  if (e->n_fl) return e->fail(RL_ESTATE, "rl_resize while a batch is in flight (call rl_wait)");
-  if (e->restoring) return e->fail(RL_ESTATE, "rl_resize between rl_restore_begin and rl_restore_end");
-  if (int rc = e->set_busy("rl_resize")) return rc;
+  if (int rc = e->quiet("rl_resize")) return rc;
   uint32_t lg4[4];
   for (int u = 0; u < 4; ++u) {
     lg4[u] = log2_slots[u] ? log2_slots[u] : e->cfg.log2_slots[u];
@@ -2419,9 +2456,7 @@ int rl_resize(rl_engine* e, const uint32_t log2_slots[4]) {
 // What every form checks first: the call's place among the batches, the arguments' shape and
 // the engine's capacities (blob_bytes only where the engine stages the blob).
 static int peek_enter(rl_engine* e, const rl_batch* b, const char* what, bool host) {
-  if (e->n_fl) return e->fail(RL_ESTATE, "%s while a batch is in flight (call rl_wait)", what);
-  if (e->restoring) return e->fail(RL_ESTATE, "%s between rl_restore_begin and rl_restore_end", what);
-  if (int rc = e->set_busy(what)) return rc;
+  if (int rc = e->quiet(what)) return rc;
   if (b->n_desc > e->cfg.max_batch_desc || b->n_req > e->cfg.max_batch_req ||
       (host && b->blob_bytes > e->cfg.max_blob_bytes))
     return e->fail(RL_ECAPACITY, "%s: batch exceeds engine capacity (%u desc, %u req, %u blob bytes)", what,
@@ -2524,8 +2559,7 @@ int rl_forget(rl_engine* e, const rl_batch* b, rl_peek_reply* out_or_null) {
 int rl_engine::set_ensure() {
   if (set_sc.index) return 0;
   const uint64_t n = cfg.max_batch_desc ? cfg.max_batch_desc : 1u;
-  uint32_t lg = 6;
-  while ((1ull << lg) < 2 * n) ++lg;
+  const uint32_t lg = index_log2(n);
   SetScratch sc{};
   rl_peek_reply* vals = nullptr;
   SetCtl* hc = nullptr;
@@ -2568,22 +2602,15 @@ static int set_gen_check(rl_engine* e, const char* what, const uint32_t gcall[8]
 static int set_plan_run(rl_engine* e, const char* what, uint32_t n, SetScratch& sc, int kt,
                         const std::function<void()>& lookup, const std::function<void(const SetScratch&)>& index) {
   sc = e->set_sc;
-  sc.log2_entries = 6;
-  while ((1ull << sc.log2_entries) < 2ull * n) ++sc.log2_entries;  // <= the allocation's: n <= max_batch_desc
+  sc.log2_entries = index_log2(n);
   hipError_t he = hipMemsetAsync(sc.index, 0, sizeof(SetEntry) << sc.log2_entries, e->stream);
   if (he == hipSuccess) he = hipMemsetAsync(sc.ctl, 0, sizeof(SetCtl), e->stream);
-  if (he == hipSuccess) {
-    // the replies first: the state before the call, for every duplicate
-    lookup();
-    e->timed(kt, [&] { index(sc); });
-    e->timed(KT_SET_PLAN, [&] { launch_set_plan(e->stream, n, e->tab, sc); });
-    he = hipGetLastError();
-  }
-  if (he == hipSuccess) he = hipMemcpyAsync(e->h_set_ctl, sc.ctl, sizeof(SetCtl), hipMemcpyDeviceToHost, e->stream);
-  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-  if (he != hipSuccess) return e->hip_fail(he, (std::string(what) + " (nothing written)").c_str());
-  if (e->timing) e->fold_marks();
-  return 0;
+  if (he != hipSuccess) return e->hip_fail(he, (std::string(what) + kNothingWritten).c_str());
+  // the replies first: the state before the call, for every duplicate
+  lookup();
+  e->timed(kt, [&] { index(sc); });
+  e->timed(KT_SET_PLAN, [&] { launch_set_plan(e->stream, n, e->tab, sc); });
+  return e->fetch_ctl(e->h_set_ctl, sc.ctl, sizeof(SetCtl), what, kNothingWritten);
 }
 
 // What the plan found on the device: one identity per index entry, the claims per region against
@@ -2611,13 +2638,8 @@ static int set_apply(rl_engine* e, const char* what, uint32_t n, const SetScratc
                      rl_peek_reply* out, const rl_peek_reply* d_rep) {
   const SetCtl* hc = e->h_set_ctl;
   e->timed(KT_SET_APPLY, [&] { launch_set_apply(e->stream, n, e->tab, sc); });
-  hipError_t he = hipGetLastError();
-  if (he == hipSuccess) he = hipMemcpyAsync(e->h_set_ctl, sc.ctl, sizeof(SetCtl), hipMemcpyDeviceToHost, e->stream);
-  if (he == hipSuccess && out)
-    he = hipMemcpyAsync(out, d_rep, (size_t)n * sizeof(rl_peek_reply), hipMemcpyDeviceToHost, e->stream);
-  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-  if (he != hipSuccess) return e->hip_fail(he, (std::string(what) + ": applying pass (the table may hold part of the call)").c_str());
-  if (e->timing) e->fold_marks();
+  const int rc = e->fetch_ctl(e->h_set_ctl, sc.ctl, sizeof(SetCtl), what, kApplyFailed, out, d_rep, n);
+  if (rc) return rc;
   if (hc->err)
     return e->fail(RL_EDEVICE, "%s: a region had no free slot left (the table may hold part of the call)", what);
   RegionOcc nocc[8];
@@ -2697,31 +2719,35 @@ int rl_set(rl_engine* e, const rl_batch* b, const rl_peek_reply* values, rl_peek
 // Routed set, the engine's two phases (rl_hip.h "Routed set"). The plan is rl_set's checking half
 // over records that arrived from every origin: what rl_set's host checks refuse is found by
 // k_set_index_routed and read here from the control block.
-int rl_set_routed_plan(rl_engine* e, const void* d_records, const rl_peek_reply* d_values, uint32_t n,
-                       rl_peek_reply* d_reply_or_null) {
-  if (!e) return RL_EINVAL;
-  const char* what = "rl_set_routed_plan";
-  if (e->n_fl) return e->fail(RL_ESTATE, "%s while a batch is in flight (call rl_wait)", what);
-  if (e->restoring) return e->fail(RL_ESTATE, "%s between rl_restore_begin and rl_restore_end", what);
-  if (e->set_open)
-    return e->fail(RL_ESTATE, "%s: a plan is open (call %s)", what,
-                   e->adj_plan ? "rl_adjust_routed_commit" : "rl_set_routed_commit");
+// What both record-form plans check first: the call's place, the engine's capacities, the form's
+// arrays (null_arrays: which of them is null, in the form's words, or nullptr), and rules and
+// scratch to run in.
+static int plan_enter(rl_engine* e, const char* what, uint32_t n, const char* null_arrays) {
+  if (int rc = e->quiet(what, true)) return rc;
   if (e->cfg.max_batch_desc > SET_MAX_DESC)
     return e->fail(RL_ECAPACITY, "%s: max_batch_desc %u above 2^29", what, e->cfg.max_batch_desc);
   if (n > e->cfg.max_batch_desc)
     return e->fail(RL_ECAPACITY, "%s: %u records exceed max_batch_desc %u", what, n, e->cfg.max_batch_desc);
-  if (n && (!d_records || !d_values)) return e->fail(RL_EINVAL, "%s: null record or value array", what);
+  if (null_arrays) return e->fail(RL_EINVAL, "%s: null %s array", what, null_arrays);
   if (!e->d_rules) {
     const int rc = rl_load_rules(e, nullptr, 0);
     if (rc) return rc;
   }
+  return n ? e->set_ensure() : 0;
+}
+
+int rl_set_routed_plan(rl_engine* e, const void* d_records, const rl_peek_reply* d_values, uint32_t n,
+                       rl_peek_reply* d_reply_or_null) {
+  if (!e) return RL_EINVAL;
+  const char* what = "rl_set_routed_plan";
+  int rc = plan_enter(e, what, n, n && (!d_records || !d_values) ? "record or value" : nullptr);
+  if (rc) return rc;
+  rl_engine::Plan& p = e->plan;
   uint32_t gcall[8] = {};
   if (n) {
-    int rc = e->set_ensure();
-    if (rc) return rc;
     const RRec* recs = reinterpret_cast<const RRec*>(d_records);
     rc = set_plan_run(
-        e, what, n, e->set_plan_sc, KT_SET_INDEX_ROUTED,
+        e, what, n, p.set_sc, KT_SET_INDEX_ROUTED,
         [&] {
           if (d_reply_or_null)
             launch_peek_routed(e->stream, recs, n, e->d_rules, e->n_rules, e->tab, d_reply_or_null, false);
@@ -2749,20 +2775,18 @@ int rl_set_routed_plan(rl_engine* e, const void* d_records, const rl_peek_reply*
     if (!rc) rc = set_plan_check(e, what, gcall);
     if (rc) return rc;
   }
-  e->set_open = true;
-  e->set_plan_n = n;
-  memcpy(e->set_plan_gen, gcall, sizeof gcall);
+  p.kind = rl_engine::Plan::SET;
+  p.n = n;
+  memcpy(p.set_gen, gcall, sizeof gcall);
   return 0;
 }
 
 int rl_set_routed_commit(rl_engine* e, int apply) {
   if (!e) return RL_EINVAL;
-  if (!e->set_open) return e->fail(RL_ESTATE, "rl_set_routed_commit without an open plan (call rl_set_routed_plan)");
-  if (e->adj_plan)
-    return e->fail(RL_ESTATE, "rl_set_routed_commit: the open plan is a routed adjust's (call rl_adjust_routed_commit)");
-  e->set_open = false;
-  if (!apply || !e->set_plan_n) return 0;
-  return set_apply(e, "rl_set_routed_commit", e->set_plan_n, e->set_plan_sc, e->set_plan_gen, nullptr, nullptr);
+  if (int rc = e->plan_take(rl_engine::Plan::SET)) return rc;
+  const rl_engine::Plan& p = e->plan;
+  if (!apply || !p.n) return 0;
+  return set_apply(e, "rl_set_routed_commit", p.n, p.set_sc, p.set_gen, nullptr, nullptr);
 }
 
 // ---- Adjust ---------------------------------------------------------------------------------
@@ -2771,6 +2795,31 @@ int rl_set_routed_commit(rl_engine* e, int apply) {
 // synchronous and an open plan is refused), the deltas in its staged-value array. k_adjust_index
 // writes nothing to the table and k_adjust_apply nothing after an index overflow, so every
 // failure reported below is one before anything changed.
+
+// The halves both forms run, the host form (rl_adjust) and the record form (rl_adjust_routed_plan /
+// rl_adjust_routed_commit), as set's above: rl_engine::adjust_index_run, then adjust_apply_run, and
+// the report from the control words either fetched.
+
+// Queue k_adjust_apply over the index, then fetch the control block (and n replies from d_rep to
+// h_rep unless null): one stream synchronise.
+static int adjust_apply_run(rl_engine* e, const char* what, bool clear_cache, bool per_key, const AdjScratch& sc,
+                            rl_peek_reply* h_rep, const rl_peek_reply* d_rep, uint32_t n) {
+  e->timed(KT_ADJUST_APPLY, [&] { launch_adjust_apply(e->stream, clear_cache, per_key, sc); });
+  return e->fetch_ctl(e->h_set_ctl, sc.ctl, sizeof(AdjCtl), what, kApplyFailed, h_rep, d_rep, n);
+}
+
+// The report's words from the control block as fetched behind the apply pass, which leaves the
+// index pass's three as they were (a plan's stay on the device until its commit).
+static void adjust_report(const rl_engine* e, rl_adjust_report& rep) {
+  const AdjCtl* hc = reinterpret_cast<const AdjCtl*>(e->h_set_ctl);
+  rep.nil = hc->w[ADJ_NIL][0];
+  rep.absent = hc->w[ADJ_ABSENT][0];
+  rep.applied = hc->w[ADJ_APPLIED][0];
+  rep.floored = hc->w[ADJ_FLOORED][0];
+  rep.capped = hc->w[ADJ_CAPPED][0];
+  rep.unfrozen = hc->w[ADJ_UNFROZEN][0];
+}
+
 int rl_adjust(rl_engine* e, const rl_batch* b, const int32_t* delta, uint32_t flags, rl_peek_reply* out,
               rl_adjust_report* report) {
   if (!e || !b) return RL_EINVAL;
@@ -2805,42 +2854,24 @@ int rl_adjust(rl_engine* e, const rl_batch* b, const int32_t* delta, uint32_t fl
   if (rc) return rc;
   static_assert(sizeof(int32_t) <= sizeof(rl_peek_reply), "the deltas fit the staged-value array");
   int32_t* d_delta = reinterpret_cast<int32_t*>(e->d_set_vals);
-  AdjScratch sc;
-  sc.index = reinterpret_cast<AdjEntry*>(e->set_sc.index);
-  sc.ctl = reinterpret_cast<AdjCtl*>(e->set_sc.ctl);
-  sc.log2_entries = 6;
-  while ((1ull << sc.log2_entries) < 2ull * b->n_desc) ++sc.log2_entries;  // <= the allocation's: n <= max_batch_desc
-  AdjCtl* hc = reinterpret_cast<AdjCtl*>(e->h_set_ctl);
+  const AdjScratch sc = e->adj_view(b->n_desc);
   hipError_t he = hipMemcpyAsync(d_delta, delta, (size_t)b->n_desc * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-  if (he == hipSuccess) he = hipMemsetAsync(sc.index, 0, sizeof(AdjEntry) << sc.log2_entries, e->stream);
-  if (he == hipSuccess) he = hipMemsetAsync(sc.ctl, 0, sizeof(AdjCtl), e->stream);
-  if (he != hipSuccess) return e->hip_fail(he, "rl_adjust (nothing written)");
-  e->timed(KT_ADJUST_INDEX, [&] {
-    launch_adjust_index(e->stream, d, e->d_rules, e->n_rules, e->cfg.hash_seed, e->tab, d_delta, out ? d_rep : nullptr,
-                        sc);
-  });
-  he = hipGetLastError();
+  if (he == hipSuccess)
+    he = e->adjust_index_run(sc, KT_ADJUST_INDEX, [&] {
+      launch_adjust_index(e->stream, d, e->d_rules, e->n_rules, e->cfg.hash_seed, e->tab, d_delta,
+                          out ? d_rep : nullptr, sc);
+    });
   if (he != hipSuccess) return e->hip_fail(he, "rl_adjust (nothing written)");
   const bool clear_cache = e->tab.local_cache && !(flags & RL_ADJUST_KEEP_CACHE);
-  e->timed(KT_ADJUST_APPLY, [&] { launch_adjust_apply(e->stream, clear_cache, false, sc); });
-  he = hipGetLastError();
-  if (he == hipSuccess) he = hipMemcpyAsync(hc, sc.ctl, sizeof(AdjCtl), hipMemcpyDeviceToHost, e->stream);
   // the replies land in pinned memory first: a refused call leaves `out` as it was
-  rl_peek_reply* h_rep = e->h_adj_rep;
-  if (he == hipSuccess && out)
-    he = hipMemcpyAsync(h_rep, d_rep, (size_t)b->n_desc * sizeof(rl_peek_reply), hipMemcpyDeviceToHost, e->stream);
-  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-  if (he != hipSuccess) return e->hip_fail(he, "rl_adjust: applying pass (the table may hold part of the call)");
-  if (e->timing) e->fold_marks();
-  if (hc->w[ADJ_ERR][0]) return e->fail(RL_EDEVICE, "rl_adjust: the call's index overflowed (nothing written)");
+  rl_peek_reply* h_rep = out ? e->h_adj_rep : nullptr;
+  rc = adjust_apply_run(e, "rl_adjust", clear_cache, false, sc, h_rep, d_rep, b->n_desc);
+  if (rc) return rc;
+  if (reinterpret_cast<const AdjCtl*>(e->h_set_ctl)->w[ADJ_ERR][0])
+    return e->fail(RL_EDEVICE, "rl_adjust: the call's index overflowed (nothing written)");
   if (out) memcpy(out, h_rep, (size_t)b->n_desc * sizeof(rl_peek_reply));
   rep.descriptors = b->n_desc;
-  rep.nil = hc->w[ADJ_NIL][0];
-  rep.absent = hc->w[ADJ_ABSENT][0];
-  rep.applied = hc->w[ADJ_APPLIED][0];
-  rep.floored = hc->w[ADJ_FLOORED][0];
-  rep.capped = hc->w[ADJ_CAPPED][0];
-  rep.unfrozen = hc->w[ADJ_UNFROZEN][0];
+  adjust_report(e, rep);
   if (report) *report = rep;
   return 0;
 }
@@ -2869,83 +2900,42 @@ int rl_route_pack_adjust(rl_engine* e, const rl_batch* b, const uint32_t* d_perm
 int rl_adjust_routed_plan(rl_engine* e, const void* d_records, uint32_t n, rl_peek_reply* d_reply_or_null) {
   if (!e) return RL_EINVAL;
   const char* what = "rl_adjust_routed_plan";
-  if (e->n_fl) return e->fail(RL_ESTATE, "%s while a batch is in flight (call rl_wait)", what);
-  if (e->restoring) return e->fail(RL_ESTATE, "%s between rl_restore_begin and rl_restore_end", what);
-  if (e->set_open)
-    return e->fail(RL_ESTATE, "%s: a plan is open (call %s)", what,
-                   e->adj_plan ? "rl_adjust_routed_commit" : "rl_set_routed_commit");
-  if (e->cfg.max_batch_desc > SET_MAX_DESC)
-    return e->fail(RL_ECAPACITY, "%s: max_batch_desc %u above 2^29", what, e->cfg.max_batch_desc);
-  if (n > e->cfg.max_batch_desc)
-    return e->fail(RL_ECAPACITY, "%s: %u records exceed max_batch_desc %u", what, n, e->cfg.max_batch_desc);
-  if (n && !d_records) return e->fail(RL_EINVAL, "%s: null record array", what);
-  if (!e->d_rules) {
-    const int rc = rl_load_rules(e, nullptr, 0);
-    if (rc) return rc;
-  }
-  e->adj_plan_absent = e->adj_plan_applied = 0;
+  int rc = plan_enter(e, what, n, n && !d_records ? "record" : nullptr);
+  if (rc) return rc;
+  rl_engine::Plan& p = e->plan;
   if (n) {
-    const int rc = e->set_ensure();
-    if (rc) return rc;
-    AdjScratch sc;
-    sc.index = reinterpret_cast<AdjEntry*>(e->set_sc.index);
-    sc.ctl = reinterpret_cast<AdjCtl*>(e->set_sc.ctl);
-    sc.log2_entries = 6;
-    while ((1ull << sc.log2_entries) < 2ull * n) ++sc.log2_entries;  // <= the allocation's: n <= max_batch_desc
-    const AdjCtl* hc = reinterpret_cast<const AdjCtl*>(e->h_set_ctl);
-    hipError_t he = hipMemsetAsync(sc.index, 0, sizeof(AdjEntry) << sc.log2_entries, e->stream);
-    if (he == hipSuccess) he = hipMemsetAsync(sc.ctl, 0, sizeof(AdjCtl), e->stream);
-    if (he == hipSuccess) {
-      e->timed(KT_ADJUST_INDEX_ROUTED, [&] {
-        launch_adjust_index_routed(e->stream, reinterpret_cast<const RRec*>(d_records), n, e->d_rules, e->n_rules,
-                                   e->tab, d_reply_or_null, sc);
-      });
-      he = hipGetLastError();
-    }
-    if (he == hipSuccess) he = hipMemcpyAsync(e->h_set_ctl, sc.ctl, sizeof(AdjCtl), hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+    const AdjScratch sc = e->adj_view(n);
+    const hipError_t he = e->adjust_index_run(sc, KT_ADJUST_INDEX_ROUTED, [&] {
+      launch_adjust_index_routed(e->stream, reinterpret_cast<const RRec*>(d_records), n, e->d_rules, e->n_rules, e->tab,
+                                 d_reply_or_null, sc);
+    });
     if (he != hipSuccess) return e->hip_fail(he, "rl_adjust_routed_plan (nothing written)");
-    if (e->timing) e->fold_marks();
-    const uint32_t err = hc->w[ADJ_ERR][0];
+    if ((rc = e->fetch_ctl(e->h_set_ctl, sc.ctl, sizeof(AdjCtl), what, kNothingWritten)) != 0) return rc;
+    const uint32_t err = reinterpret_cast<const AdjCtl*>(e->h_set_ctl)->w[ADJ_ERR][0];
     if (err & ADJ_ERR_BADREC)
       return e->fail(RL_EINVAL, "%s: a record's rule id is unknown, its time is above 0xFFFD0000 or its rule word has "
                                 "bits above 16 set (nothing written)", what);
     if (err) return e->fail(RL_EDEVICE, "%s: the call's index overflowed (nothing written)", what);
-    e->adj_plan_sc = sc;
-    e->adj_plan_absent = hc->w[ADJ_ABSENT][0];
-    e->adj_plan_applied = hc->w[ADJ_APPLIED][0];
+    p.adj_sc = sc;
   }
-  e->set_open = e->adj_plan = true;
-  e->set_plan_n = n;
+  p.kind = rl_engine::Plan::ADJUST;
+  p.n = n;
   return 0;
 }
 
 int rl_adjust_routed_commit(rl_engine* e, int apply, rl_adjust_report* report) {
   if (!e) return RL_EINVAL;
-  if (!e->set_open || !e->adj_plan)
-    return e->fail(RL_ESTATE, e->set_open ? "rl_adjust_routed_commit: the open plan is a routed set's (call "
-                                            "rl_set_routed_commit)"
-                                          : "rl_adjust_routed_commit without an open plan (call rl_adjust_routed_plan)");
-  e->set_open = e->adj_plan = false;
+  if (int rc = e->plan_take(rl_engine::Plan::ADJUST)) return rc;
   if (!apply) return 0;
+  const rl_engine::Plan& p = e->plan;
   rl_adjust_report rep;
   memset(&rep, 0, sizeof rep);
-  rep.descriptors = e->set_plan_n;
-  rep.absent = e->adj_plan_absent;
-  rep.applied = e->adj_plan_applied;
-  if (e->set_plan_n) {
-    const AdjScratch& sc = e->adj_plan_sc;
-    const AdjCtl* hc = reinterpret_cast<const AdjCtl*>(e->h_set_ctl);
-    e->timed(KT_ADJUST_APPLY, [&] { launch_adjust_apply(e->stream, e->tab.local_cache != 0, true, sc); });
-    hipError_t he = hipGetLastError();
-    if (he == hipSuccess) he = hipMemcpyAsync(e->h_set_ctl, sc.ctl, sizeof(AdjCtl), hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    if (he != hipSuccess)
-      return e->hip_fail(he, "rl_adjust_routed_commit: applying pass (the table may hold part of the call)");
-    if (e->timing) e->fold_marks();
-    rep.floored = hc->w[ADJ_FLOORED][0];
-    rep.capped = hc->w[ADJ_CAPPED][0];
-    rep.unfrozen = hc->w[ADJ_UNFROZEN][0];
+  rep.descriptors = p.n;
+  if (p.n) {
+    const int rc = adjust_apply_run(e, "rl_adjust_routed_commit", e->tab.local_cache != 0, true, p.adj_sc, nullptr,
+                                    nullptr, 0);
+    if (rc) return rc;
+    adjust_report(e, rep);
   }
   if (report) *report = rep;
   return 0;
@@ -2968,9 +2958,7 @@ int rl_peek_routed(rl_engine* e, const void* d_records, uint32_t n, rl_peek_repl
   if (!e) return RL_EINVAL;
   if (flags & ~(uint32_t)RL_PEEK_ROUTED_FORGET) return e->fail(RL_EINVAL, "unknown rl_peek_routed flags 0x%x", flags);
   const bool forget = (flags & RL_PEEK_ROUTED_FORGET) != 0;
-  if (e->n_fl) return e->fail(RL_ESTATE, "rl_peek_routed while a batch is in flight (call rl_wait)");
-  if (e->restoring) return e->fail(RL_ESTATE, "rl_peek_routed between rl_restore_begin and rl_restore_end");
-  if (int rc = e->set_busy("rl_peek_routed")) return rc;
+  if (int rc = e->quiet("rl_peek_routed")) return rc;
   if (n && (!d_records || (!forget && !d_reply))) return e->fail(RL_EINVAL, "rl_peek_routed: null record or reply array");
   if (!e->d_rules) {
     const int rc = rl_load_rules(e, nullptr, 0);
@@ -3010,9 +2998,7 @@ int rl_rule_stats_add_device(rl_engine* e, const rl_batch* b, const rl_status* d
 
 int rl_rule_stats_read(rl_engine* e, uint32_t first_rule, uint32_t n, rl_rule_stat* out, uint32_t flags) {
   if (!e) return RL_EINVAL;
-  if (e->n_fl) return e->fail(RL_ESTATE, "rl_rule_stats_read while a batch is in flight (call rl_wait)");
-  if (e->restoring) return e->fail(RL_ESTATE, "rl_rule_stats_read between rl_restore_begin and rl_restore_end");
-  if (int rc = e->set_busy("rl_rule_stats_read")) return rc;
+  if (int rc = e->quiet("rl_rule_stats_read")) return rc;
   if (flags & ~(uint32_t)RL_RULE_STATS_CLEAR) return e->fail(RL_EINVAL, "unknown rl_rule_stats_read flags 0x%x", flags);
   if ((uint64_t)first_rule + n > e->n_rules)
     return e->fail(RL_EINVAL, "rl_rule_stats_read: rules [%u, %llu) of %u loaded", first_rule,
@@ -3043,9 +3029,7 @@ int rl_cache_stats_add_device(rl_engine* e, const rl_batch* b, const rl_status* 
 
 int rl_cache_stats_read(rl_engine* e, rl_cache_stats* out, uint32_t flags) {
   if (!e) return RL_EINVAL;
-  if (e->n_fl) return e->fail(RL_ESTATE, "rl_cache_stats_read while a batch is in flight (call rl_wait)");
-  if (e->restoring) return e->fail(RL_ESTATE, "rl_cache_stats_read between rl_restore_begin and rl_restore_end");
-  if (int rc = e->set_busy("rl_cache_stats_read")) return rc;
+  if (int rc = e->quiet("rl_cache_stats_read")) return rc;
   if (flags & ~(uint32_t)RL_CACHE_STATS_CLEAR) return e->fail(RL_EINVAL, "unknown rl_cache_stats_read flags 0x%x", flags);
   if (!out) return e->fail(RL_EINVAL, "rl_cache_stats_read: null output");
   memset(out, 0, sizeof *out);
@@ -3067,9 +3051,7 @@ int rl_census(rl_engine* e, int64_t now, rl_census_report* out) {
   if (out->struct_size != sizeof(rl_census_report))
     return e->fail(RL_EINVAL, "rl_census: struct_size %u, expected %zu", out->struct_size, sizeof(rl_census_report));
   if (now < 0 || now > MAX_NOW) return e->fail(RL_EINVAL, "rl_census: time %lld outside [0, 0xFFFD0000]", (long long)now);
-  if (e->n_fl) return e->fail(RL_ESTATE, "rl_census while a batch is in flight (call rl_wait)");
-  if (e->restoring) return e->fail(RL_ESTATE, "rl_census between rl_restore_begin and rl_restore_end");
-  if (int rc = e->set_busy("rl_census")) return rc;
+  if (int rc = e->quiet("rl_census")) return rc;
   hipError_t he = hipSuccess;
   if (!e->d_census) {
     he = hipMalloc(&e->d_census, sizeof(CensusCtl));

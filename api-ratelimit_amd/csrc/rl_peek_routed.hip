@@ -13,33 +13,20 @@ namespace rlhip {
 namespace peek {
 
 // Three dependent levels, each one run of loads waited for once (latency-bound, random 32-B
-// reads, like k_peek): the record (32 B), then the rule entry at a clamped id, then the key's
-// first table slot (peek_key). The key string's identity comes from the record exactly as the
-// owner's decision path takes it (rl_tile.h load_routed / key_of): the rule by rrec_rule, the
-// window start from rec.now and the rule's unit, fp_final over the record's lanes. A record
-// whose rule id is not below n_rules (RL_NIL_RULE included: a pack never sends one) or whose time
-// is above MAX_NOW gets RL_PEEK_BAD and zeros and indexes nothing (the rule table holds >= 1
-// entry, host-checked). No LDS, no lane waits for another; the one loop is the probe, bounded by
-// the region size.
+// reads, like k_peek): rl_peek.h's rec_front (the record, then the rule entry), then the key's
+// first table slot (peek_key). A record that is not ok gets RL_PEEK_BAD and zeros. No LDS, no lane
+// waits for another; the one loop is the probe, bounded by the region size.
 template <bool FORGET>
 __global__ __launch_bounds__(NT) void k_peek_routed(const RRec* __restrict__ recs, const uint32_t n,
                                                     const DevRule* __restrict__ rules, const uint32_t n_rules,
                                                     const TableDesc tab, rl_peek_reply* __restrict__ out) {
   const uint32_t i = blockIdx.x * NT + threadIdx.x;
   if (i >= n) return;
-  const RRec rc = recs[i];
-  const uint32_t rl = rrec_rule(rc.rule);
-  const bool rule_ok = rl < n_rules;
-  const DevRule rr = rules[rule_ok ? rl : 0u];  // never indexed with a bad id
-  const bool ok = rule_ok && (int64_t)rc.now <= MAX_NOW;
-  // One use of the record's lanes and the rule entry ahead of the branch on `ok` (k_peek): without
-  // it the compiler loads only the record's upper half first and fetches the lanes behind the
-  // branch, a round trip of their own.
-  asm volatile("" ::"v"(rc.a), "v"(rc.b), "v"(rr.unit), "v"(rr.div));
+  const RecFront f = rec_front(recs, rules, n_rules, i, true, false);
   rl_peek_reply rep;
   rep.count = rep.ttl_s = rep.cached_s = 0u;
   rep.flags = RL_PEEK_BAD;
-  if (ok) rep = peek_key<FORGET>(FpState{rc.a, rc.b}, rc.now, rr, tab, rep);
+  if (f.ok) rep = peek_key<FORGET>(FpState{f.rc.a, f.rc.b}, f.rc.now, f.rr, tab, rep);
   if (!FORGET) out[i] = rep;
 }
 
@@ -60,7 +47,6 @@ __global__ __launch_bounds__(NT) void k_peek_unpack(const uint32_t n, const uint
 
 }  // namespace peek
 
-// out: n replies (unused by the forget launch). Launches nothing for n == 0.
 void launch_peek_routed(hipStream_t st, const RRec* recs, uint32_t n, const DevRule* rules, uint32_t n_rules,
                         const TableDesc& tab, rl_peek_reply* out, bool forget) {
   if (!n) return;

@@ -32,46 +32,24 @@ RL_DEV void count_regions(bool on, uint32_t region, uint32_t (*cnt)[64]) {
   }
 }
 
-// The loads go out as k_peek's do (rl_peek.hip): (offsets, rule id, request index, the value),
-// then (now, the rule entry, the prefix's first 32 bytes), every one unconditional at a clamped
-// index; then the index probe (rl_set_index.h set_index_tail, shared with k_set_index_routed).
+// The value is read beside the first level of rl_peek.h's desc_front; behind the front comes the
+// index probe (rl_set_index.h set_index_tail, shared with k_set_index_routed).
 __global__ __launch_bounds__(NT) void k_set_index(const DevBatch in, const DevRule* __restrict__ rules,
                                                   const uint32_t n_rules, const uint64_t seed, const TableDesc tab,
                                                   const rl_peek_reply* __restrict__ values, const SetScratch sc) {
   const uint32_t i = blockIdx.x * NT + threadIdx.x;
   if (i >= in.n_desc) return;
-  const uint32_t rl = in.rule[i];
-  const uint32_t q = in.req_of[i];
-  const uint32_t qp = in.req_of[i ? i - 1u : 0u];
-  const uint32_t oa = in.off[i];
-  const uint32_t ob = in.off[i + 1u];
   const rl_peek_reply v = values[i];
-
-  const bool nil = rl == RL_NIL_RULE;
-  const bool rule_ok = rl < n_rules, q_ok = q < in.n_req;
-  const bool lay = oa <= ob && ob <= in.blob_bytes && qp <= q;
-  bool ok = !nil && rule_ok && q_ok && lay;
-  const uint32_t o0 = ok ? oa : 0u, len = ok ? ob - oa : 0u;
-  const int64_t now = in.now[q_ok ? q : 0u];
-  const DevRule rr = rules[rule_ok ? rl : 0u];  // never indexed with a bad id
-  const u32x4* p = reinterpret_cast<const u32x4*>(in.blob + (o0 & ~3u));
-  const u32x4 w0 = p[0];
-  const u32x4 w1 = *reinterpret_cast<const u32x4*>(reinterpret_cast<const uint32_t*>(p) + 4);
-
-  ok = ok && now >= 0 && now <= MAX_NOW;
-  // (k_peek: keeps the level's loads in front of the branch on `ok`)
-  asm volatile("" ::"v"(rr.unit), "v"(rr.div), "v"(w0.x), "v"(w0.y), "v"(w0.z), "v"(w0.w), "v"(w1.x), "v"(w1.y),
-               "v"(w1.z), "v"(w1.w));
+  const peek::DescFront f = peek::desc_front(in, rules, n_rules, i);
   const bool wc = !(v.flags & RL_SET_KEEP_COUNTER);
   const bool wf = !(v.flags & RL_SET_KEEP_CACHE) && tab.local_cache;
   SetDesc d;
   d.ent = SETD_NONE;
   d.tag = 0u;
-  if (ok && (wc || wf)) {  // the host refused a malformed descriptor (and value) before the launch
-    const uint32_t t = (uint32_t)now;
-    const FpState s = prefix_state_pre(w0, w1, in.blob, o0, len, seed);
-    const peek::KeyIdent id = peek::key_ident(s, t, rr);
-    d = set_index_tail(i, id, t, v, wc, wf, per_second_store(tab, rr.unit), sc);
+  if (f.ok && (wc || wf)) {  // the host refused a malformed descriptor (and value) before the launch
+    const FpState s = prefix_state_pre(f.w0, f.w1, in.blob, f.o0, f.len, seed);
+    const peek::KeyIdent id = peek::key_ident(s, f.now, f.rr);
+    d = set_index_tail(i, id, f.now, v, wc, wf, per_second_store(tab, f.rr.unit), sc);
   }
   sc.desc[i] = d;
 }

@@ -17,11 +17,10 @@ namespace set {
 constexpr int NTR = peek::NT;
 
 // Two dependent levels of loads, each waited for once: the record (32 B) with its value (16 B),
-// then the rule entry at a clamped id; then set_index_tail's index probe. The identity comes from
-// the record as k_peek_routed takes it: no prefix hashing, no blob. Record index i is origin-major,
-// then descriptor order inside the origin (the pack keeps serial order inside an owner's group, the
-// exchange is origin-major), so "largest index wins" is "the last SET wins, the origins' batches one
-// after another in shard order".
+// then the rule entry at a clamped id (rl_peek.h rec_front); then set_index_tail's index probe.
+// Record index i is origin-major, then descriptor order inside the origin (the pack keeps serial
+// order inside an owner's group, the exchange is origin-major), so "largest index wins" is "the
+// last SET wins, the origins' batches one after another in shard order".
 //
 // The owner's host sees neither records nor values, so what rl_set checks on the host is checked
 // here: a malformed record or value sets an error bit and indexes nothing, and the window
@@ -39,16 +38,11 @@ __global__ __launch_bounds__(NTR) void k_set_index_routed(const RRec* __restrict
   const uint32_t i = blockIdx.x * NTR + threadIdx.x;
   const bool in = i < n;
   const uint32_t ic = in ? i : n - 1u;  // n >= 1: the launch is skipped for an empty call
-  const RRec rc = recs[ic];
   const rl_peek_reply v = values[ic];
-  const uint32_t rl = rrec_rule(rc.rule);
-  const bool rule_ok = rl < n_rules;
-  const DevRule rr = rules[rule_ok ? rl : 0u];  // never indexed with a bad id
-  const bool rec_ok = rule_ok && (int64_t)rc.now <= MAX_NOW;
-  // One use of the record's lanes and the rule entry ahead of the branches (k_peek_routed): without
-  // it the compiler loads only the record's upper half first and fetches the lanes behind the
-  // branch, a round trip of their own.
-  asm volatile("" ::"v"(rc.a), "v"(rc.b), "v"(rr.unit), "v"(rr.div));
+  const peek::RecFront f = peek::rec_front(recs, rules, n_rules, ic, true, false);
+  const RRec& rc = f.rc;
+  const DevRule& rr = f.rr;
+  const bool rec_ok = f.ok;
   const uint32_t t = rc.now;
   const bool wc = !(v.flags & RL_SET_KEEP_COUNTER);
   const bool wf = !(v.flags & RL_SET_KEEP_CACHE) && tab.local_cache;
