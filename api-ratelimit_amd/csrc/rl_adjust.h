@@ -33,7 +33,9 @@ struct AdjCtl {
 };
 static_assert(sizeof(AdjCtl) <= sizeof(SetCtl), "the adjust control block lives in rl_set's");
 constexpr uint32_t ADJ_ERR_INDEX = 1u;  // the index had no entry left for a pair (unreachable: 2^k >= 2 n)
-constexpr uint32_t ADJ_ERR_BADREC = 2u;  // the record form: a malformed record (rule id, time or rule word's upper bits)
+constexpr uint32_t ADJ_ERR_BADREC = 2u;  // the record form: a malformed record (rule id, time or rule word's upper bits);
+                                         // a flight: a malformed descriptor of a device batch
+constexpr uint32_t ADJ_ERR_POISON = 4u;  // a flight behind a batch the engine reruns: nothing ran, the engine runs it again
 
 struct AdjScratch {
   AdjEntry* index;
@@ -48,6 +50,13 @@ void launch_adjust_index(hipStream_t st, const rl_batch& b, const DevRule* rules
 // clear_cache: the call's cache part is on (the local cache is on and RL_ADJUST_KEEP_CACHE is not set).
 // per_key: a pair's cache part also needs its entry's count to be non-zero (a routed plan's commit).
 void launch_adjust_apply(hipStream_t st, bool clear_cache, bool per_key, const AdjScratch& sc);
+
+// An adjust in flight (rl_engine.cpp adjust_queue): pass 0 is the index kernel, pass 1 the applying
+// one, both in the form that reads the engine's poison word first (rl_adjust.hip FLIGHT). Launches
+// nothing for n_desc == 0.
+void launch_adjust_flight(hipStream_t st, const rl_batch& b, const DevRule* rules, uint32_t n_rules, uint64_t seed,
+                          const TableDesc& tab, const int32_t* delta, rl_peek_reply* out, bool clear_cache,
+                          const AdjScratch& sc, const uint32_t* poison, int pass);
 
 // The record form (rl_adjust_routed.hip): n routed records (RRec) whose h word is the delta and
 // whose rule word's bit 16 is RL_ADJUST_KEEP_CACHE. out: n replies in device memory, or nullptr.

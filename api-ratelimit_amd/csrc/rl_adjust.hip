@@ -11,6 +11,12 @@
 // descriptor order nor scheduling. Nothing is ever claimed. Kernel boundaries order the two: no
 // lane waits for another lane or block, and every loop is bounded by the prefix length (hash), the
 // region size (probe) or the index size (insert).
+// FLIGHT: the forms an adjust in flight runs (rl_hip.h "Adjust in flight"), queued on the engine
+// stream between decision batches. Both read the poison word first (k4_place sets it for a batch
+// the engine will rerun, rl_kernels_v4.hip): behind such a batch they write nothing, neither table
+// nor replies, leave the word as it is for the batch behind them and set ADJ_ERR_POISON, and the
+// engine runs the adjust again behind the batch's rerun. The device form's descriptors come
+// unchecked: a malformed one sets ADJ_ERR_BADREC, after which the applying pass writes nothing.
 #include <hip/hip_runtime.h>
 
 #include "rl_adjust.h"
@@ -24,11 +30,18 @@ namespace adjust {
 // The front is written out here: through desc_front the kernel compiled to another load order and
 // measured 1 % slower ("By-key refactor"). A thread past n_desc reads descriptor
 // n_desc - 1 and uses nothing of it (`live`): it stays for the block's sums.
+template <bool FLIGHT>
 __global__ __launch_bounds__(NT) void k_adjust_index(const DevBatch in, const DevRule* __restrict__ rules,
                                                      const uint32_t n_rules, const uint64_t seed, const TableDesc tab,
                                                      const int32_t* __restrict__ delta, rl_peek_reply* __restrict__ out,
-                                                     const AdjScratch sc) {
+                                                     const AdjScratch sc, const uint32_t* __restrict__ poison) {
   const uint32_t gi = blockIdx.x * NT + threadIdx.x;
+  if constexpr (FLIGHT) {
+    if (*poison) {  // the same word for every thread: the whole grid leaves
+      if (gi == 0u) atomicOr(&sc.ctl->w[ADJ_ERR][0], ADJ_ERR_POISON);
+      return;
+    }
+  }
   const bool live = gi < in.n_desc;
   const uint32_t i = live ? gi : in.n_desc - 1u;  // n_desc >= 1 in a launched kernel
   const uint32_t rl = in.rule[i];
@@ -50,6 +63,9 @@ __global__ __launch_bounds__(NT) void k_adjust_index(const DevBatch in, const De
   const u32x4 w1 = *reinterpret_cast<const u32x4*>(reinterpret_cast<const uint32_t*>(p) + 4);
 
   ok = ok && now >= 0 && now <= MAX_NOW;
+  if constexpr (FLIGHT) {
+    if (live && !nil && !ok) atomicOr(&sc.ctl->w[ADJ_ERR][0], ADJ_ERR_BADREC);
+  }
   // (k_peek: keeps the level's loads in front of the branch on `ok`)
   asm volatile("" ::"v"(rr.unit), "v"(rr.div), "v"(w0.x), "v"(w0.y), "v"(w0.z), "v"(w0.w), "v"(w1.x), "v"(w1.y),
                "v"(w1.z), "v"(w1.w));
@@ -71,9 +87,16 @@ __global__ __launch_bounds__(NT) void k_adjust_index(const DevBatch in, const De
 // PER_KEY (a routed plan's commit, rl_adjust_routed.hip): a pair's cache part also needs the
 // entry's count, there "found records of the pair that came without RL_ADJUST_KEEP_CACHE", to be
 // non-zero; the host form's flag is the call's, folded into clear_cache.
-template <bool PER_KEY>
-__global__ __launch_bounds__(NT) void k_adjust_apply(const bool clear_cache, const AdjScratch sc) {
+template <bool PER_KEY, bool FLIGHT>
+__global__ __launch_bounds__(NT) void k_adjust_apply(const bool clear_cache, const AdjScratch sc,
+                                                     const uint32_t* __restrict__ poison) {
   const uint32_t i = blockIdx.x * NT + threadIdx.x;
+  if constexpr (FLIGHT) {
+    if (*poison) {
+      if (i == 0u) atomicOr(&sc.ctl->w[ADJ_ERR][0], ADJ_ERR_POISON);
+      return;
+    }
+  }
   bool floored = false, capped = false, unfrozen = false;
   if (i < (1u << sc.log2_entries) && !sc.ctl->w[ADJ_ERR][0]) {
     const uint4 a = reinterpret_cast<const uint4*>(sc.index + i)[0];
@@ -104,15 +127,32 @@ void launch_adjust_index(hipStream_t st, const rl_batch& b, const DevRule* rules
   if (!b.n_desc) return;
   const DevBatch in = make_dev_batch(b);
   const uint32_t grid = (b.n_desc + adjust::NT - 1u) / adjust::NT;
-  hipLaunchKernelGGL(adjust::k_adjust_index, dim3(grid), dim3(adjust::NT), 0, st, in, rules, n_rules, seed, tab, delta,
-                     out, sc);
+  hipLaunchKernelGGL(adjust::k_adjust_index<false>, dim3(grid), dim3(adjust::NT), 0, st, in, rules, n_rules, seed, tab,
+                     delta, out, sc, nullptr);
 }
 void launch_adjust_apply(hipStream_t st, bool clear_cache, bool per_key, const AdjScratch& sc) {
   const uint32_t grid = ((1u << sc.log2_entries) + adjust::NT - 1u) / adjust::NT;
   if (per_key)
-    hipLaunchKernelGGL(adjust::k_adjust_apply<true>, dim3(grid), dim3(adjust::NT), 0, st, clear_cache, sc);
+    hipLaunchKernelGGL((adjust::k_adjust_apply<true, false>), dim3(grid), dim3(adjust::NT), 0, st, clear_cache, sc,
+                       nullptr);
   else
-    hipLaunchKernelGGL(adjust::k_adjust_apply<false>, dim3(grid), dim3(adjust::NT), 0, st, clear_cache, sc);
+    hipLaunchKernelGGL((adjust::k_adjust_apply<false, false>), dim3(grid), dim3(adjust::NT), 0, st, clear_cache, sc,
+                       nullptr);
+}
+void launch_adjust_flight(hipStream_t st, const rl_batch& b, const DevRule* rules, uint32_t n_rules, uint64_t seed,
+                          const TableDesc& tab, const int32_t* delta, rl_peek_reply* out, bool clear_cache,
+                          const AdjScratch& sc, const uint32_t* poison, int pass) {
+  if (!b.n_desc) return;
+  if (pass == 0) {
+    const DevBatch in = make_dev_batch(b);
+    const uint32_t grid = (b.n_desc + adjust::NT - 1u) / adjust::NT;
+    hipLaunchKernelGGL(adjust::k_adjust_index<true>, dim3(grid), dim3(adjust::NT), 0, st, in, rules, n_rules, seed, tab,
+                       delta, out, sc, poison);
+  } else {
+    const uint32_t grid = ((1u << sc.log2_entries) + adjust::NT - 1u) / adjust::NT;
+    hipLaunchKernelGGL((adjust::k_adjust_apply<false, true>), dim3(grid), dim3(adjust::NT), 0, st, clear_cache, sc,
+                       poison);
+  }
 }
 
 }  // namespace rlhip

@@ -67,6 +67,9 @@ struct PendingCall {
   std::vector<PeekStatus> peek;
   std::vector<rl_peek_reply> set_vals;
   std::vector<int32_t> deltas;
+  // HipRateLimitCache::AdjustQueued: an adjust that waits in the queue like a DoLimit (prefix,
+  // limits and deltas as above, answered into `peek`); keep: RL_ADJUST_KEEP_CACHE
+  bool adj_queued = false, keep = false;
 };
 
 namespace {
@@ -169,6 +172,34 @@ bool setup_jitter(HipSettings& s) {
 uint16_t draw_jitter(const HipSettings& s) { return (uint16_t)s.jitter_rand(s.expiration_jitter_max_seconds); }
 
 }  // namespace
+
+// The batch being built in one of the engine's pinned staging slots (rl_host_acquire_c, or
+// rl_host_acquire for the full format): calls are written straight into C memory, the way the Go
+// batcher does (INTEGRATION.md §3). The compact wire format (rl_batch_c) is the default; a batch
+// whose first call does not fit it goes as rl_batch.
+struct HipRateLimitCache::Staged {
+  std::vector<std::shared_ptr<PendingCall>> calls;
+  bool compact = true;
+  rl_host_batch hb{};      // full format
+  rl_host_batch_c hc{};    // compact format
+  uint32_t nd = 0, nr = 0, nb = 0;
+  uint32_t max_desc = 0, max_req = 0, max_blob = 0;
+  int64_t tmin = 0, tmax = 0;
+  bool one_per_req = true;  // compact: every request so far holds one descriptor (req_of implicit)
+  bool failed = false;      // refused at submit: its callers already have the error
+  uint64_t seq = 0;         // gathered (and submitted) in this order
+  bool adjust = false;      // an rl_adjust_submit flight of queued adjusts (calls, nd and failed only)
+};
+
+// The queued adjusts of one gather with one keep flag: one rl_batch in plain memory, one request
+// per call (rl_adjust_submit copies it).
+struct HipRateLimitCache::AdjGather {
+  std::vector<std::shared_ptr<PendingCall>> calls;
+  std::vector<uint8_t> blob;
+  std::vector<uint32_t> off{0u}, rule, req_of;
+  std::vector<int64_t> now;
+  std::vector<int32_t> delta;
+};
 
 HipRateLimitCache::HipRateLimitCache(const HipSettings& s, std::shared_ptr<TimeSource> ts)
     : s_(s), ts_(std::move(ts)) {
@@ -389,9 +420,10 @@ void HipRateLimitCache::autogrow(std::deque<Staged>& inflight) {
 }
 
 void HipRateLimitCache::finish_oldest(std::deque<Staged>& inflight) {
+  const bool adjust = inflight.front().adjust;
   finish(inflight.front());
   inflight.pop_front();
-  autogrow(inflight);
+  if (!adjust) autogrow(inflight);  // an adjust claims nothing
 }
 
 // Peek / Forget / Set: the request's descriptors as one rl_batch of one request, built and handed
@@ -503,6 +535,114 @@ std::vector<HipRateLimitCache::PeekStatus> HipRateLimitCache::Adjust(
   return peek_call(request, limits, false, nullptr, keep_cache || fc_ ? (uint32_t)RL_ADJUST_KEEP_CACHE : 0u, &deltas);
 }
 
+// AdjustQueued: the call waits in the queue like a DoLimit; the submitter gathers it (add_adjust)
+// and answers it when its flight completes (finish).
+std::vector<HipRateLimitCache::PeekStatus> HipRateLimitCache::AdjustQueued(
+    const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits,
+    const std::vector<int32_t>& deltas, bool keep_cache) {
+  if (request.Descriptors.size() != limits.size())
+    throw std::logic_error("assert: len(request.Descriptors) == len(limits)");
+  if (deltas.size() != limits.size()) throw std::logic_error("assert: len(deltas) == len(limits)");
+  auto call = std::make_shared<PendingCall>();
+  call->req = &request;
+  call->limits = &limits;
+  call->adj_queued = true;
+  call->keep = keep_cache || fc_;  // HIP_LOCAL_CACHE=freecache: the device cache is unused
+  call->deltas = deltas;
+  call->prefix.resize(limits.size());
+  for (size_t i = 0; i < limits.size(); ++i) {
+    if (!limits[i]) continue;
+    std::string& p = call->prefix[i];  // GenerateCacheKey prefix  cache_key.go:57-65
+    p = request.Domain;
+    p += '_';
+    for (const auto& e : request.Descriptors[i].Entries) {
+      p += e.Key;
+      p += '_';
+      p += e.Value;
+      p += '_';
+    }
+  }
+  std::future<void> f = call->done.get_future();
+  {
+    std::lock_guard<std::mutex> g(mu_);
+    q_.push_back(call);
+    ++inflight_;
+  }
+  cv_.notify_one();
+  f.get();  // rethrows RedisError
+  return std::move(call->peek);
+}
+
+// A group is cut in front of a call that would take it past HIP_BATCH_LIMIT descriptors; a call
+// larger than that goes alone, and the engine refuses it.
+bool HipRateLimitCache::fits_adjust(const AdjGather& g, const PendingCall& c) const {
+  return g.calls.empty() || g.rule.size() + c.prefix.size() <= s_.batch_limit;
+}
+
+// One queued adjust into its gather's group: one request, at the time read here.
+void HipRateLimitCache::add_adjust(AdjGather& g, const std::shared_ptr<PendingCall>& cp, uint64_t seq) {
+  PendingCall& c = *cp;
+  const uint32_t r = (uint32_t)g.calls.size();
+  if (trace_) trace_(c.req, seq, kTraceAdjust | (c.keep ? kTraceAdjustKeep : 0u) | r);
+  g.now.push_back(ts_->UnixNow());
+  for (size_t i = 0; i < c.prefix.size(); ++i) {
+    const auto& lim = (*c.limits)[i];
+    g.blob.insert(g.blob.end(), c.prefix[i].begin(), c.prefix[i].end());
+    g.off.push_back((uint32_t)g.blob.size());
+    g.rule.push_back(lim ? rule_id(lim->Limit, lim->ShadowMode) : RL_NIL_RULE);
+    g.req_of.push_back(r);
+    g.delta.push_back(c.deltas[i]);
+  }
+  g.calls.push_back(cp);
+}
+
+// Hand a gather's group to the engine as one flight (rl_adjust_submit), as submit() hands a batch:
+// new rules first, one drain-and-retry on RL_ESTATE, any other refusal fails the group's calls.
+HipRateLimitCache::Staged HipRateLimitCache::submit_adjust(AdjGather& g, bool keep, uint64_t seq,
+                                                           std::deque<Staged>& inflight) {
+  Staged st;
+  st.adjust = true;
+  st.seq = seq;
+  st.nd = (uint32_t)g.rule.size();
+  st.calls = std::move(g.calls);
+  g.blob.resize(g.blob.size() + RL_BLOB_SLACK, 0);  // (never read past blob_bytes on the host; keeps data() non-null)
+  rl_batch b;
+  memset(&b, 0, sizeof b);
+  b.n_desc = st.nd;
+  b.n_req = (uint32_t)st.calls.size();
+  b.blob_bytes = g.off.back();
+  b.prefix_blob = g.blob.data();
+  b.prefix_off = g.off.data();
+  b.rule_id = g.rule.data();
+  b.req_of = g.req_of.data();
+  b.now = g.now.data();
+  for (int attempt = 0;; ++attempt) {
+    int rc = 0;
+    if (rules_dirty_) {
+      rc = rl_load_rules(eng_, rules_.data(), (uint32_t)rules_.size());
+      if (!rc) {
+        rules_dirty_ = false;
+        n_loads_ += 1;
+        if (!inflight.empty()) n_loads_inflight_ += 1;
+      }
+    }
+    if (!rc) rc = rl_adjust_submit(eng_, &b, g.delta.data(), keep ? (uint32_t)RL_ADJUST_KEEP_CACHE : 0u, 1);
+    if (rc == RL_ESTATE && attempt == 0 && !inflight.empty()) {
+      while (!inflight.empty()) {
+        finish(inflight.front());
+        inflight.pop_front();
+      }
+      n_drains_ += 1;
+      continue;
+    }
+    if (rc) {
+      fail(st.calls);
+      st.failed = true;
+    }
+    return st;
+  }
+}
+
 DoLimitResponse HipRateLimitCache::DoLimit(const RateLimitRequest& request,
                                            const std::vector<std::shared_ptr<RateLimit>>& limits) {
   auto call = make_call(request, limits, *ts_);
@@ -541,23 +681,6 @@ uint32_t HipRateLimitCache::rule_id(const RateLimitLimit& l, bool shadow) {
   rules_dirty_ = true;
   return id;
 }
-
-// The batch being built in one of the engine's pinned staging slots (rl_host_acquire_c, or
-// rl_host_acquire for the full format): calls are written straight into C memory, the way the Go
-// batcher does (INTEGRATION.md §3). The compact wire format (rl_batch_c) is the default; a batch
-// whose first call does not fit it goes as rl_batch.
-struct HipRateLimitCache::Staged {
-  std::vector<std::shared_ptr<PendingCall>> calls;
-  bool compact = true;
-  rl_host_batch hb{};      // full format
-  rl_host_batch_c hc{};    // compact format
-  uint32_t nd = 0, nr = 0, nb = 0;
-  uint32_t max_desc = 0, max_req = 0, max_blob = 0;
-  int64_t tmin = 0, tmax = 0;
-  bool one_per_req = true;  // compact: every request so far holds one descriptor (req_of implicit)
-  bool failed = false;      // refused at submit: its callers already have the error
-  uint64_t seq = 0;         // gathered (and submitted) in this order
-};
 
 static int64_t compact_base(int64_t first_now) { return first_now > 0 ? first_now - 1 : 0; }
 
@@ -721,6 +844,31 @@ void HipRateLimitCache::submit(Staged& st, std::deque<Staged>& inflight) {
 // memory (no copy), read here before the next submit reuses the slot.
 void HipRateLimitCache::finish(Staged& st) {
   if (st.failed) return;
+  if (st.adjust) {
+    // nothing was applied when the flight fails: every call of it gets the error
+    adj_rep_.resize(st.nd ? st.nd : 1u);
+    if (rl_wait_adjust(eng_, adj_rep_.data(), nullptr)) {
+      fail(st.calls);
+      return;
+    }
+    size_t d = 0;
+    for (auto& cp : st.calls) {
+      PendingCall& c = *cp;
+      c.peek.resize(c.prefix.size());
+      for (size_t i = 0; i < c.prefix.size(); ++i, ++d) {
+        const rl_peek_reply& r = adj_rep_[d];
+        PeekStatus& s = c.peek[i];
+        s.Found = (r.flags & RL_PEEK_FOUND) != 0;
+        s.LocalCached = (r.flags & RL_PEEK_LOCAL_CACHED) != 0;
+        s.Count = r.count;
+        s.TtlSeconds = r.ttl_s;
+        s.CachedSeconds = r.cached_s;
+      }
+      c.done.set_value();
+    }
+    done_calls(st.calls.size());
+    return;
+  }
   const rl_status* out = nullptr;
   const uint32_t* thr = nullptr;
   if (st.compact) {
@@ -850,23 +998,36 @@ void HipRateLimitCache::submitter() {
       done_calls(1);
       continue;
     }
+    // a flight of either kind takes a slot: the one acquired here is free once at most two are in flight
+    while (inflight.size() >= RL_MAX_IN_FLIGHT) finish_oldest(inflight);
     Staged st;
     st.seq = staged_seq_++;
-    st.compact = compactable(*first);
-    if (st.compact ? rl_host_acquire_c(eng_, &st.hc) : rl_host_acquire(eng_, &st.hb)) {
+    AdjGather ag[2];  // the gather's queued adjusts without / with keep_cache
+    // The slot in both layouts (the same memory): the first decision call picks one. A gather of
+    // adjusts alone leaves it unused.
+    if (rl_host_acquire_c(eng_, &st.hc) || rl_host_acquire(eng_, &st.hb)) {
       std::vector<std::shared_ptr<PendingCall>> one{first};
       fail(one);
       continue;
     }
-    st.max_desc = st.compact ? st.hc.max_desc : st.hb.max_desc;
-    st.max_req = st.compact ? st.hc.max_req : st.hb.max_req;
-    st.max_blob = st.compact ? st.hc.max_blob : st.hb.max_blob;
-    if (first->prefix.size() > st.max_desc || first->blob_bytes > st.max_blob) {
-      first->done.set_exception(std::make_exception_ptr(RedisError("hip backend: request larger than a batch")));
-      done_calls(1);
-      continue;
+    // the first decision call of the gather: the batch's format and the slot's room (false: a request no slot holds)
+    auto begin_decision = [&](const PendingCall& c) {
+      st.compact = compactable(c);
+      st.max_desc = st.compact ? st.hc.max_desc : st.hb.max_desc;
+      st.max_req = st.compact ? st.hc.max_req : st.hb.max_req;
+      st.max_blob = st.compact ? st.hc.max_blob : st.hb.max_blob;
+      return c.prefix.size() <= st.max_desc && c.blob_bytes <= st.max_blob;
+    };
+    if (first->adj_queued) {
+      add_adjust(ag[first->keep], first, st.seq);
+    } else {
+      if (!begin_decision(*first)) {
+        first->done.set_exception(std::make_exception_ptr(RedisError("hip backend: request larger than a batch")));
+        done_calls(1);
+        continue;
+      }
+      add(st, first);
     }
-    add(st, first);
     {
       std::unique_lock<std::mutex> g(mu_);
       const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(s_.batch_window_us);
@@ -874,11 +1035,17 @@ void HipRateLimitCache::submitter() {
         while (!q_.empty()) {
           std::shared_ptr<PendingCall> c = q_.front();
           q_.pop_front();
-          if (c->ctl || !fits(st, *c)) {
+          // (a decision call the slot cannot hold as the batch's first is refused as the next gather's first)
+          const bool ok = c->ctl          ? false
+                          : c->adj_queued ? fits_adjust(ag[c->keep], *c)
+                          : st.calls.empty() ? begin_decision(*c)
+                                             : fits(st, *c);
+          if (!ok) {
             carry = std::move(c);  // starts the next batch (a control call: runs after this one)
             goto full;
           }
-          add(st, c);
+          if (c->adj_queued) add_adjust(ag[c->keep], c, st.seq);
+          else add(st, c);
         }
         if (stop_ || st.nd >= s_.batch_limit) break;
         if (!inflight.empty() && s_.answer_early) {
@@ -899,9 +1066,26 @@ void HipRateLimitCache::submitter() {
       }
     full:;
     }
-    submit(st, inflight);
-    inflight.push_back(std::move(st));
-    if (inflight.size() == 2) finish_oldest(inflight);
+    // The decision batch first: it was built in the slot of the next flight. The adjust flights go
+    // behind it; all calls of one gather are concurrent, so that is a legal serial order, and the
+    // trace hook's positions say so (kTraceAdjust sorts behind every request position).
+    const uint64_t seq = st.seq;
+    if (!st.calls.empty()) {
+      submit(st, inflight);
+      inflight.push_back(std::move(st));
+    }
+    for (int k = 0; k < 2; ++k) {
+      if (ag[k].calls.empty()) continue;
+      while (inflight.size() >= RL_MAX_IN_FLIGHT) finish_oldest(inflight);
+      inflight.push_back(submit_adjust(ag[k], k == 1, seq, inflight));
+    }
+    // one decision batch stays in flight while the next is gathered, as before; with it at most one other flight
+    auto decisions = [&] {
+      size_t n = 0;
+      for (auto& f : inflight) n += f.adjust ? 0u : 1u;
+      return n;
+    };
+    while (decisions() >= 2 || inflight.size() >= RL_MAX_IN_FLIGHT) finish_oldest(inflight);
   }
   for (auto& st : inflight) finish(st);
 }

@@ -270,6 +270,25 @@ class HipRateLimitCache : public RateLimitCache {
   std::vector<PeekStatus> Adjust(const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits,
                                  const std::vector<int32_t>& deltas, bool keep_cache = false);
 
+  // AdjustQueued (rl_hip.h "Adjust in flight"): Adjust without emptying the pipeline. The call goes
+  // into the queue like a DoLimit. The submitter's gather takes the queued calls of both kinds:
+  // DoLimits form the decision batch, queued adjusts one adjust batch per keep flag, one request per
+  // call at the time read on the submitter thread, and each adjust batch goes to the engine as one
+  // rl_adjust_submit flight BEHIND the gather's decision batch (the decision batch is built in the
+  // staging slot of the next flight, so it has to go first; all calls in the queue at one gather
+  // are concurrent, so this is a legal serial order). Nothing is drained. The trace hook reports
+  // (the gather's sequence number, kTraceAdjust | kTraceAdjustKeep for keep_cache | the call's
+  // index in its group): behind every DoLimit position of that gather, the group without
+  // keep_cache first. Different from Adjust: the corrections gathered into one engine call ARE one
+  // call: summed per (string, store), clamped once, and every reply is the state before that engine
+  // call. A failed flight fails every call in it with RedisError; nothing was applied and the cache
+  // keeps serving. HIP_LOCAL_CACHE=freecache forces keep_cache, as in Adjust. No auto-grow check
+  // runs behind it. Out of scope: HipRoutedRateLimitCache, the Python mirror, a compact wire form.
+  static constexpr uint32_t kTraceAdjust = 0x80000000u, kTraceAdjustKeep = 0x40000000u;
+  std::vector<PeekStatus> AdjustQueued(const RateLimitRequest& request,
+                                       const std::vector<std::shared_ptr<RateLimit>>& limits,
+                                       const std::vector<int32_t>& deltas, bool keep_cache = false);
+
   // Resize (rl_hip.h "Resize"): the counter table moved into one of log2_slots[u] slots per window
   // generation for home unit u (0 keeps that unit's size), on the device, every counter kept. A
   // control call like Save / Load: every DoLimit enqueued before it is decided first, rl_resize
@@ -343,6 +362,11 @@ class HipRateLimitCache : public RateLimitCache {
 
  private:
   struct Staged;
+  struct AdjGather;
+  bool fits_adjust(const AdjGather& g, const PendingCall& c) const;
+  void add_adjust(AdjGather& g, const std::shared_ptr<PendingCall>& c, uint64_t seq);
+  Staged submit_adjust(AdjGather& g, bool keep, uint64_t seq, std::deque<Staged>& inflight);
+  std::vector<rl_peek_reply> adj_rep_;  // a completed adjust flight's replies (submitter thread)
   void submitter();
   void control(std::function<std::string()> f);
   std::vector<PeekStatus> peek_call(const RateLimitRequest& request,

@@ -190,6 +190,14 @@ struct rl_engine {
   AdjScratch adj_view(uint32_t n) const {
     return AdjScratch{reinterpret_cast<AdjEntry*>(set_sc.index), index_log2(n), reinterpret_cast<AdjCtl*>(set_sc.ctl)};
   }
+  // An adjust in flight (rl_hip.h "Adjust in flight") takes a host slot as a batch does. Per slot: a
+  // pinned copy of the flight's control block, fetched on the stream behind its applying pass, and
+  // for the host form pinned and device staging of the deltas (4 B x max_batch_desc each). Allocated
+  // at the first call that needs them and kept.
+  AdjCtl* h_adj_ctl[RL_MAX_IN_FLIGHT] = {};
+  int32_t* h_adj_delta[RL_MAX_IN_FLIGHT] = {};
+  int32_t* d_adj_delta[RL_MAX_IN_FLIGHT] = {};
+  int adj_flight_ensure(bool host);
   // The plan between rl_set_routed_plan / rl_adjust_routed_plan and its commit. Its index and its
   // control block stay in rl_set's scratch, so while one is open the engine refuses what an open
   // restore refuses (quiet, set_busy).
@@ -424,6 +432,12 @@ struct rl_engine {
     uint32_t* user_thr = nullptr;
     bool poll = false;             // completion = k4_group's done word behind h_ctl (no event)
     uint32_t count = 0;            // COUNT_*: k_rule_stats / k_cache_stats run behind the batch's pipeline
+    // an adjust flight: b's arrays, these and the slot's control-block copy are all of it (out, thr and
+    // reply stay null); host: the host form, whose replies pass through the slot's pinned outputs
+    bool adjust = false;
+    const int32_t* adj_delta = nullptr;  // device
+    rl_peek_reply* adj_rep = nullptr;    // device, or null
+    bool adj_clear = false;              // the call's cache part is on
   };
   Flight fl[HSLOTS];
   // A device v4 batch completes on the word k4_group's last block writes behind the slot's pinned
@@ -549,7 +563,11 @@ struct rl_engine {
   int upload_hot(hipStream_t us);
   void update_hot(const HotCand* cand, uint32_t n_cand);
   int settle(Flight& f);
-  int finish(rl_status* out, uint32_t* thr, bool into);
+  int finish(rl_status* out, uint32_t* thr, bool into, rl_peek_reply* adj_out = nullptr,
+             rl_adjust_report* adj_report = nullptr);
+  int adjust_queue(const Flight& f);
+  int adjust_settle(Flight& f);
+  int adjust_submit(const rl_batch& d, const int32_t* d_delta, uint32_t flags, rl_peek_reply* d_rep, bool host);
   int enqueue_d2h(const Flight& f, hipStream_t s);
   int check_batch(const rl_batch* b, bool host);
   int submit_common(const rl_batch& d, rl_status* out, uint32_t* thr, RReply* reply, hipEvent_t in_ev,
@@ -926,6 +944,7 @@ int rl_engine::enqueue_d2h(const Flight& f, hipStream_t s) {
 // prefix run held two fingerprints. Reruns are synchronous, so they are on the table before
 // anything submitted later.
 int rl_engine::settle(Flight& f) {
+  if (f.adjust) return adjust_settle(f);
   h_ctl = h_ctl_s[f.slot];
   h_cand = h_cand_s[f.slot];
   hipError_t e = timing ? hipStreamSynchronize(stream) : f.poll ? poll_done(f) : wait_event_polling(done_ev[f.slot]);
@@ -971,10 +990,13 @@ int rl_engine::settle(Flight& f) {
   return 0;
 }
 
+static void adjust_report(const AdjCtl* hc, rl_adjust_report& rep);  // (with rl_adjust, below)
+
 // Complete the oldest in-flight batch: reruns (settle), then errors, hot-set maintenance,
 // stats and the host-path copy. A refused batch poisons the batch behind it (k4_place ->
 // k4_scan), so that one is settled here too, before anything else can be submitted.
-int rl_engine::finish(rl_status* out_into, uint32_t* thr_into, bool into) {
+int rl_engine::finish(rl_status* out_into, uint32_t* thr_into, bool into, rl_peek_reply* adj_out,
+                      rl_adjust_report* adj_report) {
   Flight f = fl[0];
   for (int q = 1; q < n_fl; ++q) fl[q - 1] = fl[q];
   --n_fl;
@@ -989,7 +1011,9 @@ int rl_engine::finish(rl_status* out_into, uint32_t* thr_into, bool into) {
     for (int q = 0; q < n_fl && !fl[q].settled; ++q) {  // refused in turn (poison chain)
       int rc = settle(fl[q]);
       if (rc) return rc;
-      if (!fl[q].fell_back) break;
+      // (an adjust that skipped its write fell back too; an empty one launched nothing that could
+      // read the poison word, so the chain goes on through it)
+      if (!fl[q].fell_back && !(fl[q].adjust && !fl[q].b.n_desc)) break;
       hipError_t e2 = hipMemsetAsync(d_poison, 0, 4, stream);
       if (e2 != hipSuccess) return hip_fail(e2, "hipMemsetAsync(poison)");
     }
@@ -1001,6 +1025,21 @@ int rl_engine::finish(rl_status* out_into, uint32_t* thr_into, bool into) {
     hipError_t e = hipStreamSynchronize(stream);  // the next batch's marks too
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
     fold_marks();
+  }
+  if (f.adjust) {  // nothing was claimed: no hot-set, occupancy or stats work behind it
+    if (errs & ADJ_ERR_BADREC)
+      return fail(RL_EINVAL, "adjust in flight: a descriptor with an unknown rule id or request index, malformed "
+                             "prefix offsets / request order, or a time outside [0, 0xFFFD0000] (nothing written)");
+    if (errs & ADJ_ERR_INDEX) return fail(RL_EDEVICE, "adjust in flight: the call's index overflowed (nothing written)");
+    if (errs & ADJ_ERR_POISON) return fail(RL_EDEVICE, "adjust in flight: refused again behind its batch's rerun");
+    if (adj_out && f.host && f.adj_rep && f.b.n_desc)
+      memcpy(adj_out, stage[f.slot].h_out, (size_t)f.b.n_desc * sizeof(rl_peek_reply));
+    if (adj_report) {
+      memset(adj_report, 0, sizeof *adj_report);
+      adj_report->descriptors = f.b.n_desc;
+      adjust_report(h_adj_ctl[f.slot], *adj_report);
+    }
+    return 0;
   }
   if (errs & ERR_BAD_INPUT)
     return fail(RL_EINVAL, "batch references an unknown rule id or request index, or malformed prefix offsets / "
@@ -1363,6 +1402,9 @@ void rl_destroy(rl_engine* e) {
     hipFree(e->d_hot_buf[k]);
     hipHostFree(e->h_cand_s[k]);
     hipHostFree(e->h_ctl_s[k]);
+    hipHostFree(e->h_adj_ctl[k]);
+    hipHostFree(e->h_adj_delta[k]);
+    hipFree(e->d_adj_delta[k]);
   }
   for (auto& g : e->stage) {
     hipFree(g.d_cin);
@@ -1564,6 +1606,7 @@ int rl_query(rl_engine* e) {
 int rl_wait_into(rl_engine* e, rl_status* out, uint32_t* req_throttle_ms) {
   if (!e) return RL_EINVAL;
   if (!e->n_fl) return e->fail(RL_ESTATE, "rl_wait_into without a batch in flight");
+  if (e->fl[0].adjust) return e->fail(RL_ESTATE, "rl_wait_into: the oldest flight is an adjust (rl_wait_adjust)");
   if (e->fl[0].raw) return e->fail(RL_ESTATE, "rl_wait_into: the oldest batch is compact (rl_wait_raw_into)");
   return e->finish(out, req_throttle_ms, true);
 }
@@ -1574,7 +1617,7 @@ int rl_wait_view(rl_engine* e, const rl_status** out, const uint32_t** req_throt
   *req_throttle_ms = nullptr;
   if (!e->n_fl) return e->fail(RL_ESTATE, "rl_wait_view without a batch in flight");
   const rl_engine::Flight& f = e->fl[0];
-  if (!f.host || f.raw || f.user_out || f.user_thr)
+  if (f.adjust || !f.host || f.raw || f.user_out || f.user_thr)
     return e->fail(RL_ESTATE, "rl_wait_view: the oldest batch is not a host batch submitted without output pointers");
   const uint32_t s = f.slot;
   int rc = e->finish(nullptr, nullptr, true);  // (into, with no targets: no copy)
@@ -1790,7 +1833,7 @@ int rl_submit_pipelined(rl_engine* e, const rl_batch* b, rl_status* d_out, uint3
   if (e->n_fl && e->default_mode() != MODE_V4)
     return e->fail(RL_ESTATE, "a second batch in flight needs the v4 pipeline (call rl_wait)");
   for (int q = 0; q < e->n_fl; ++q)
-    if (e->fl[q].out == d_out || e->fl[q].thr == d_req_throttle_ms)
+    if (!e->fl[q].adjust && (e->fl[q].out == d_out || e->fl[q].thr == d_req_throttle_ms))
       return e->fail(RL_EINVAL, "batches in flight together need distinct output buffers");
   return e->submit_common(*b, d_out, d_req_throttle_ms, nullptr, nullptr, true, false, nullptr, nullptr);
 }
@@ -2455,8 +2498,13 @@ int rl_resize(rl_engine* e, const uint32_t log2_slots[4]) {
 // ---- Peek / forget ------------------------------------------------------------------------
 // What every form checks first: the call's place among the batches, the arguments' shape and
 // the engine's capacities (blob_bytes only where the engine stages the blob).
+static int peek_args(rl_engine* e, const rl_batch* b, const char* what, bool host);
 static int peek_enter(rl_engine* e, const rl_batch* b, const char* what, bool host) {
   if (int rc = e->quiet(what)) return rc;
+  return peek_args(e, b, what, host);
+}
+// (the part an adjust in flight shares: its place among the flights has its own rules)
+static int peek_args(rl_engine* e, const rl_batch* b, const char* what, bool host) {
   if (b->n_desc > e->cfg.max_batch_desc || b->n_req > e->cfg.max_batch_req ||
       (host && b->blob_bytes > e->cfg.max_blob_bytes))
     return e->fail(RL_ECAPACITY, "%s: batch exceeds engine capacity (%u desc, %u req, %u blob bytes)", what,
@@ -2810,8 +2858,7 @@ static int adjust_apply_run(rl_engine* e, const char* what, bool clear_cache, bo
 
 // The report's words from the control block as fetched behind the apply pass, which leaves the
 // index pass's three as they were (a plan's stay on the device until its commit).
-static void adjust_report(const rl_engine* e, rl_adjust_report& rep) {
-  const AdjCtl* hc = reinterpret_cast<const AdjCtl*>(e->h_set_ctl);
+static void adjust_report(const AdjCtl* hc, rl_adjust_report& rep) {
   rep.nil = hc->w[ADJ_NIL][0];
   rep.absent = hc->w[ADJ_ABSENT][0];
   rep.applied = hc->w[ADJ_APPLIED][0];
@@ -2871,9 +2918,182 @@ int rl_adjust(rl_engine* e, const rl_batch* b, const int32_t* delta, uint32_t fl
     return e->fail(RL_EDEVICE, "rl_adjust: the call's index overflowed (nothing written)");
   if (out) memcpy(out, h_rep, (size_t)b->n_desc * sizeof(rl_peek_reply));
   rep.descriptors = b->n_desc;
-  adjust_report(e, rep);
+  adjust_report(reinterpret_cast<const AdjCtl*>(e->h_set_ctl), rep);
   if (report) *report = rep;
   return 0;
+}
+
+// ---- Adjust in flight -------------------------------------------------------------------------
+// rl_adjust_pipelined / rl_adjust_submit / rl_wait_adjust (rl_hip.h "Adjust in flight", DESIGN.md
+// §4h). The adjust is a flight: it takes a sequence number and the host slot that goes with it, as
+// a batch does, so every rule run_pipeline keeps by position (batch seq-2 is fl[n_fl - 2] and
+// done_ev[(seq - 2) % HSLOTS]; device slot seq & 1; control block seq % 3) holds with adjusts among
+// the batches. Both kernels are queued on the engine stream, where every table access of a batch is
+// too, so the adjust sees the table its place in submission order gives it. It completes on the
+// slot's event, behind the copy of its control block into the slot's pinned copy; the next adjust's
+// memsets of the shared index and control block are behind that copy on the same stream.
+
+int rl_engine::adj_flight_ensure(bool host) {
+  if (int rc = set_ensure()) return rc;
+  const size_t n = cfg.max_batch_desc ? cfg.max_batch_desc : 1u;
+  hipError_t he = hipSuccess;
+  for (int k = 0; k < HSLOTS && he == hipSuccess; ++k) {
+    if (!h_adj_ctl[k]) he = hipHostMalloc(&h_adj_ctl[k], sizeof(AdjCtl), hipHostMallocDefault);
+    if (he == hipSuccess && host && !h_adj_delta[k])
+      he = hipHostMalloc(&h_adj_delta[k], n * sizeof(int32_t), hipHostMallocDefault);
+    if (he == hipSuccess && host && !d_adj_delta[k]) he = hipMalloc(&d_adj_delta[k], n * sizeof(int32_t));
+  }
+  if (he == hipSuccess) return 0;
+  (void)hipGetLastError();  // (what was allocated stays for the next call and rl_destroy)
+  return hip_fail(he, "adjust flight staging allocation");
+}
+
+// Queue the flight's two kernels and the copies behind them: at its submit, and again, behind the
+// rerun of the batch that poisoned it, from settle.
+int rl_engine::adjust_queue(const Flight& f) {
+  AdjCtl* hc = h_adj_ctl[f.slot];
+  const uint32_t n = f.b.n_desc;
+  if (!n) {  // (the slot's previous flight is complete: nothing is still copying into hc)
+    memset(hc, 0, sizeof(AdjCtl));
+    return 0;
+  }
+  const AdjScratch sc = adj_view(n);
+  hipError_t he = adjust_index_run(sc, KT_ADJUST_INDEX, [&] {
+    launch_adjust_flight(stream, f.b, d_rules, n_rules, cfg.hash_seed, tab, f.adj_delta, f.adj_rep, f.adj_clear, sc,
+                         d_poison, 0);
+  });
+  if (he != hipSuccess) return hip_fail(he, "adjust in flight (nothing written)");
+  timed(KT_ADJUST_APPLY, [&] {
+    launch_adjust_flight(stream, f.b, d_rules, n_rules, cfg.hash_seed, tab, f.adj_delta, f.adj_rep, f.adj_clear, sc,
+                         d_poison, 1);
+  });
+  he = hipGetLastError();
+  if (he == hipSuccess) he = hipMemcpyAsync(hc, sc.ctl, sizeof(AdjCtl), hipMemcpyDeviceToHost, stream);
+  if (he == hipSuccess && f.host && f.adj_rep)
+    he = hipMemcpyAsync(stage[f.slot].h_out, f.adj_rep, (size_t)n * sizeof(rl_peek_reply), hipMemcpyDeviceToHost,
+                        stream);
+  if (he != hipSuccess) return hip_fail(he, (std::string("adjust in flight") + kApplyFailed).c_str());
+  return 0;
+}
+
+// settle()'s part for an adjust flight: wait for it, and run it again if it found the poison word
+// set. finish() has rerun the batch ahead and cleared the word by then, and the rerun is
+// synchronous, so it is on the table before the flight behind is looked at.
+int rl_engine::adjust_settle(Flight& f) {
+  hipError_t e = timing ? hipStreamSynchronize(stream) : wait_event_polling(done_ev[f.slot]);
+  if (e != hipSuccess) return hip_fail(e, "hipEventSynchronize");
+  uint32_t errs = h_adj_ctl[f.slot]->w[ADJ_ERR][0];
+  if (errs & ADJ_ERR_POISON) {
+    f.fell_back = true;  // for the chain; not an lsd_fallback
+    int rc = adjust_queue(f);
+    if (rc) return rc;
+    e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+    errs = h_adj_ctl[f.slot]->w[ADJ_ERR][0];
+  }
+  f.errs = errs;
+  f.settled = true;
+  return 0;
+}
+
+int rl_engine::adjust_submit(const rl_batch& d, const int32_t* d_delta, uint32_t flags, rl_peek_reply* d_rep,
+                             bool host) {
+  if (resolve_pending) {  // rule ids from an rl_resolve_device on the front stream
+    const hipError_t we = hipStreamWaitEvent(stream, ev_resolve, 0);
+    if (we != hipSuccess) return hip_fail(we, "hipStreamWaitEvent(resolve)");
+    resolve_pending = false;
+  }
+  const uint32_t s = (uint32_t)(sub_seq % HSLOTS);
+  Flight f;
+  f.adjust = true;
+  f.b = d;
+  f.adj_delta = d_delta;
+  f.adj_rep = d_rep;
+  f.adj_clear = tab.local_cache && !(flags & RL_ADJUST_KEEP_CACHE);
+  f.slot = s;
+  f.host = host;
+  int rc = adjust_queue(f);
+  if (rc) return rc;
+  // k4_group of a batch clears the control block of the batch two behind it; in its place:
+  hipError_t e = hipMemsetAsync(v4_ctl[(sub_seq + 2) % 3], 0, sizeof(EngineCtl), stream);
+  done_ev[s] = ev_done[s];
+  if (e == hipSuccess) e = hipEventRecord(done_ev[s], stream);
+  if (e != hipSuccess) return hip_fail(e, "hipEventRecord(done)");
+  fl[n_fl++] = f;
+  ++sub_seq;
+  return 0;
+}
+
+// What both submit forms check, in rl_adjust's order behind the flight rules.
+static int adjust_flight_enter(rl_engine* e, const rl_batch* b, const int32_t* delta, uint32_t flags, const char* what,
+                               bool host) {
+  if (e->n_fl >= HSLOTS) return e->fail(RL_ESTATE, "%s with %d flights in flight (call rl_wait)", what, HSLOTS);
+  if (e->restoring) return e->fail(RL_ESTATE, "%s between rl_restore_begin and rl_restore_end", what);
+  if (int rc = e->set_busy(what)) return rc;
+  if (int rc = peek_args(e, b, what, host)) return rc;
+  if (e->cfg.max_batch_desc > SET_MAX_DESC)
+    return e->fail(RL_ECAPACITY, "%s: max_batch_desc %u above 2^29", what, e->cfg.max_batch_desc);
+  if (b->n_desc && !delta) return e->fail(RL_EINVAL, "%s: null delta array", what);
+  if (flags & ~(uint32_t)RL_ADJUST_KEEP_CACHE) return e->fail(RL_EINVAL, "%s: unknown flag bits 0x%x", what, flags);
+  if (e->n_fl && e->default_mode() != MODE_V4)
+    return e->fail(RL_ESTATE, "%s: an adjust behind another flight needs the v4 pipeline (call rl_wait)", what);
+  return 0;
+}
+
+int rl_adjust_pipelined(rl_engine* e, const rl_batch* b, const int32_t* d_delta, uint32_t flags,
+                        rl_peek_reply* d_reply_or_null) {
+  if (!e || !b) return RL_EINVAL;
+  int rc = adjust_flight_enter(e, b, d_delta, flags, "rl_adjust_pipelined", false);
+  if (rc) return rc;
+  if ((rc = e->adj_flight_ensure(false)) != 0) return rc;
+  return e->adjust_submit(*b, d_delta, flags, d_reply_or_null, false);
+}
+
+int rl_adjust_submit(rl_engine* e, const rl_batch* b, const int32_t* delta, uint32_t flags, int want_replies) {
+  if (!e || !b) return RL_EINVAL;
+  const char* what = "rl_adjust_submit";
+  int rc = adjust_flight_enter(e, b, delta, flags, what, true);
+  if (rc) return rc;
+  if ((rc = peek_check(e, b, what)) != 0) return rc;
+  if ((rc = e->adj_flight_ensure(true)) != 0) return rc;
+  const uint32_t s = (uint32_t)(e->sub_seq % HSLOTS);
+  rl_engine::Stage& g = e->stage[s];
+  e->acquired = -1;
+  rl_batch d = *b;
+  d.hits_addend = nullptr;
+  d.ttl_jitter = nullptr;
+  if (!b->n_desc) return e->adjust_submit(d, nullptr, flags, nullptr, true);
+  // Into the slot's pinned memory unless the caller built the batch there (rl_host_acquire), as
+  // rl_submit stages; the copies go on the engine stream, in front of the kernels.
+  uint8_t* h = g.h_in;
+  struct Arr { const void* src; size_t o, n; } arrs[] = {
+      {b->prefix_blob, 0, b->blob_bytes}, {b->prefix_off, e->o_off, ((size_t)b->n_desc + 1) * 4},
+      {b->rule_id, e->o_rule, (size_t)b->n_desc * 4}, {b->req_of, e->o_req, (size_t)b->n_desc * 4},
+      {b->now, e->o_now, (size_t)b->n_req * 8}};
+  for (auto& a : arrs)
+    if (a.n && a.src != h + a.o) memcpy(h + a.o, a.src, a.n);
+  memset(h + b->blob_bytes, 0, RL_BLOB_SLACK);  // the device reads prefixes in 16-B words
+  arrs[0].n += RL_BLOB_SLACK;
+  memcpy(e->h_adj_delta[s], delta, (size_t)b->n_desc * sizeof(int32_t));
+  hipError_t he = hipMemcpyAsync(e->d_adj_delta[s], e->h_adj_delta[s], (size_t)b->n_desc * sizeof(int32_t),
+                                 hipMemcpyHostToDevice, e->stream);
+  for (auto& a : arrs)
+    if (he == hipSuccess) he = hipMemcpyAsync(g.d_in + a.o, h + a.o, a.n, hipMemcpyHostToDevice, e->stream);
+  if (he != hipSuccess) return e->hip_fail(he, "rl_adjust_submit staging");
+  d.prefix_blob = g.d_in;
+  d.prefix_off = reinterpret_cast<const uint32_t*>(g.d_in + e->o_off);
+  d.rule_id = reinterpret_cast<const uint32_t*>(g.d_in + e->o_rule);
+  d.req_of = reinterpret_cast<const uint32_t*>(g.d_in + e->o_req);
+  d.now = reinterpret_cast<const int64_t*>(g.d_in + e->o_now);
+  return e->adjust_submit(d, e->d_adj_delta[s], flags,
+                          want_replies ? reinterpret_cast<rl_peek_reply*>(g.d_out) : nullptr, true);
+}
+
+int rl_wait_adjust(rl_engine* e, rl_peek_reply* out_or_null, rl_adjust_report* report_or_null) {
+  if (!e) return RL_EINVAL;
+  if (!e->n_fl) return e->fail(RL_ESTATE, "rl_wait_adjust without a flight in flight");
+  if (!e->fl[0].adjust) return e->fail(RL_ESTATE, "rl_wait_adjust: the oldest flight is a batch (rl_wait)");
+  return e->finish(nullptr, nullptr, false, out_or_null, report_or_null);
 }
 
 // Routed adjust, the engine's pieces (rl_hip.h "Routed adjust"). The plan is rl_adjust up to and
@@ -2935,7 +3155,7 @@ int rl_adjust_routed_commit(rl_engine* e, int apply, rl_adjust_report* report) {
     const int rc = adjust_apply_run(e, "rl_adjust_routed_commit", e->tab.local_cache != 0, true, p.adj_sc, nullptr,
                                     nullptr, 0);
     if (rc) return rc;
-    adjust_report(e, rep);
+    adjust_report(reinterpret_cast<const AdjCtl*>(e->h_set_ctl), rep);
   }
   if (report) *report = rep;
   return 0;

@@ -312,6 +312,9 @@ ABI = [
     ("rl_set", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_void_p], C.c_int),
     ("rl_adjust", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(RlAdjustReport)],
      C.c_int),
+    ("rl_adjust_pipelined", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_uint32, C.c_void_p], C.c_int),
+    ("rl_adjust_submit", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_uint32, C.c_int], C.c_int),
+    ("rl_wait_adjust", [C.c_void_p, C.c_void_p, C.POINTER(RlAdjustReport)], C.c_int),
     ("rl_peek_routed", [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32], C.c_int),
     ("rl_route_unpack_peek", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     ("rl_router_peek", [C.c_void_p, C.POINTER(RlBatch), C.POINTER(C.c_void_p)], C.c_int),
@@ -844,6 +847,51 @@ class Engine:
         s = _batch_struct(b)
         self._check(self.lib.rl_adjust(self.h, C.byref(s), _ptr(d) or None, ADJUST_KEEP_CACHE if keep_cache else 0,
                                        (_ptr(out) or None) if want_out else None, C.byref(rep)), "rl_adjust")
+        return out, {f: int(getattr(rep, f)) for f in ADJUST_REPORT_FIELDS}
+
+    # ---- adjust in flight (rl_hip.h "Adjust in flight") ----
+    def adjust_pipelined(self, n_desc: int, n_req: int, blob_bytes: int, ptrs, delta_ptr: int,
+                         keep_cache: bool = False, reply_ptr: int = 0):
+        """rl_adjust_pipelined: adjust() of an rl_batch of device pointers (ptrs = blob, off, rule,
+        req_of, now, hits or 0) with n_desc int32 deltas at delta_ptr, queued as a flight between the
+        batches in flight; the replies (PEEK_DTYPE) go to device memory at reply_ptr unless 0.
+        wait_adjust() (or wait()) completes it; the arrays stay as they are until then."""
+        s = RlBatch()
+        s.n_desc, s.n_req, s.blob_bytes, s.reserved = n_desc, n_req, blob_bytes, 0
+        _set_ptrs(s, ptrs)
+        self._check(self.lib.rl_adjust_pipelined(self.h, C.byref(s), delta_ptr or None,
+                                                 ADJUST_KEEP_CACHE if keep_cache else 0, reply_ptr or None),
+                    "rl_adjust_pipelined")
+
+    def adjust_submit(self, b: Batch, delta, keep_cache: bool = False, want_out: bool = True):
+        """rl_adjust_submit: adjust() of a host batch as a flight (the arrays are copied before the call
+        returns). want_out keeps the replies for wait_adjust()."""
+        d = np.asarray(delta)
+        if d.shape != (b.n_desc,):
+            raise ValueError(f"rl_adjust_submit: {d.shape[0] if d.ndim == 1 else d.shape} deltas for "
+                             f"{b.n_desc} descriptors")
+        if d.size and (d.dtype.kind not in "iu" or int(d.min()) < -2**31 or int(d.max()) > 2**31 - 1):
+            raise ValueError("rl_adjust_submit: a delta is not an int32")
+        d = np.ascontiguousarray(d, np.int32)
+        s = _batch_struct(b)
+        self._check(self.lib.rl_adjust_submit(self.h, C.byref(s), _ptr(d) or None,
+                                              ADJUST_KEEP_CACHE if keep_cache else 0, int(bool(want_out))),
+                    "rl_adjust_submit")
+
+    def wait_adjust(self):
+        """rl_wait_adjust: complete the oldest flight, which must be an adjust. Returns (the replies
+        (PEEK_DTYPE) of an adjust_submit with want_out, else None; the report as a dict of
+        ADJUST_REPORT_FIELDS)."""
+        # (the binding keeps no list of the flights: the engine is given room for the largest call,
+        # and a first reply that still holds the marker says that it kept none)
+        if getattr(self, "_adj_buf", None) is None:
+            self._adj_buf = np.zeros(max(1, self.cfg.max_batch_desc), PEEK_DTYPE)
+        buf = self._adj_buf
+        buf["flags"][0] = 0xFFFFFFFF
+        rep = RlAdjustReport()
+        self._check(self.lib.rl_wait_adjust(self.h, _ptr(buf), C.byref(rep)), "rl_wait_adjust")
+        n = int(rep.descriptors)
+        out = buf[:n].copy() if n and buf["flags"][0] != 0xFFFFFFFF else None
         return out, {f: int(getattr(rep, f)) for f in ADJUST_REPORT_FIELDS}
 
     def peek_device(self, n_desc: int, n_req: int, blob_bytes: int, ptrs, out_ptr: int):

@@ -929,8 +929,8 @@ int rl_set(rl_engine* e, const rl_batch* host_batch, const rl_peek_reply* values
  * rl_peek's free host staging slot; the replies pass through 16 B x max_batch_desc of pinned memory,
  * allocated at the first call that asks for them.
  * The routed forms (rl_router_adjust; rl_adjust_routed_plan / _commit over routed records) are
- * "Routed adjust" below. Out of scope: a device-memory form, adjusting while batches are in flight,
- * a compact wire form. */
+ * "Routed adjust" below; the device-memory form and adjusting while batches are in flight are
+ * "Adjust in flight" below. Out of scope: a compact wire form. */
 enum { RL_ADJUST_KEEP_CACHE = 1u };
 typedef struct rl_adjust_report {   /* 64 B */
   uint64_t descriptors;  /* n_desc of the call */
@@ -944,6 +944,64 @@ typedef struct rl_adjust_report {   /* 64 B */
 } rl_adjust_report;      /* descriptors == nil + absent + applied */
 int rl_adjust(rl_engine* e, const rl_batch* host_batch, const int32_t* delta, uint32_t flags,
               rl_peek_reply* out_or_null, rl_adjust_report* report_or_null);
+
+/* ---- Adjust in flight ---------------------------------------------------------
+ * rl_adjust without stopping the engine: the adjust is queued between the batches in flight and
+ * completes in its turn. A cost limiter makes about one adjust per decision (the true-up or refund
+ * when a request ends); with rl_adjust each of them waits out the pipeline first.
+ *
+ * Semantics are rl_adjust's, word for word, taken at the call's place in submission order among the
+ * flights: identity, the found rule, the per-pair 64-bit sum, the clamp, the cache part and the
+ * report. Nothing is claimed; rl_engine_stats, rule stats and cache stats are not touched.
+ *
+ * rl_adjust_pipelined: the batch's arrays and d_delta (n_desc words) are device memory, as for
+ * rl_submit_pipelined; hits_addend and ttl_jitter are not read. d_reply_or_null receives the n_desc
+ * replies in device memory. Returns at once. The kernels run on the engine stream, behind everything
+ * queued there. The caller leaves the arrays alone until the flight's wait has returned (a flight
+ * behind a refused batch reads them again).
+ * rl_adjust_submit: host memory. The batch's arrays are the rl_host_acquire slot's (no copy) or any
+ * host memory (copied before the call returns); delta is always copied, through 4 B x max_batch_desc
+ * of pinned and of device staging per slot, allocated at the first call and kept. want_replies != 0
+ * keeps the replies for rl_wait_adjust. The call stages through the slot rl_host_acquire hands out
+ * and consumes it, as rl_submit does: a batch that is being built in an acquired slot and is not
+ * this call's is overwritten, so a caller that builds a decision batch in place submits that batch
+ * first and the adjust behind it (the batcher's order, rl_cache.hpp AdjustQueued).
+ * rl_wait_adjust: completes the oldest flight, which must be an adjust. out (host form with
+ * want_replies only; may be NULL) receives the replies, *report (may be NULL) the report.
+ *
+ * Flights: a flight of either kind counts towards RL_MAX_IN_FLIGHT, and one more returns RL_ESTATE.
+ * rl_wait completes an adjust flight and discards its report; rl_query works on it. rl_wait_into,
+ * rl_wait_view and rl_wait_raw_* on an adjust flight, and rl_wait_adjust on a batch, return RL_ESTATE
+ * and complete nothing. Everything that needs the engine quiet keeps returning RL_ESTATE while an
+ * adjust is in flight (the synchronous by-key calls, snapshot begin, restore, merge, resize, census,
+ * the stats reads, rl_set_stream, the routed plans). Both submit calls return RL_ESTATE with a
+ * restore or a routed plan open (the adjust runs in rl_set's scratch), and, behind another flight,
+ * without the v4 pipeline (RL_CFG_LSD_ONLY, or too many rules: rl_submit_pipelined's rule). With
+ * nothing in flight they are legal in every mode.
+ *
+ * Refused at once, no flight added: rl_adjust's list (RL_ECAPACITY: the capacities, max_batch_desc
+ * above 2^29; RL_EINVAL: reserved, null arrays, unknown flag bits), and for the host form everything
+ * rl_adjust refuses of a batch's contents. The device form cannot see the contents: a malformed
+ * descriptor (rule id at or above the loaded count and not RL_NIL_RULE, request index at or above
+ * n_req, req_of decreasing, offsets out of order or past blob_bytes, time outside [0, 0xFFFD0000])
+ * gets RL_PEEK_BAD, the applying pass writes nothing at all, and the wait returns RL_EINVAL;
+ * d_reply still holds the state before the call for the well-formed descriptors. So the call is all
+ * or nothing, as rl_adjust is. A refused or failed host-form flight leaves out untouched.
+ * n_desc == 0 is a legal empty flight with a zero report.
+ * RL_EHIP from either submit call (a launch or copy the runtime refused) adds no flight, but what
+ * was queued before the failure still runs, as after such a failure in rl_adjust's applying pass:
+ * the table may hold the call.
+ *
+ * Order against a refused batch: a batch the bucketed pipeline refuses is rerun by the host at its
+ * wait, after everything queued behind it has run on the device. An adjust queued behind such a batch
+ * finds the batch's poison word set, writes nothing (neither table nor replies) and is run again by
+ * the wait, behind the batch's rerun and before the flight behind it, so the serial order holds.
+ * Such an adjust does not count in rl_engine_stats.lsd_fallbacks. */
+int rl_adjust_pipelined(rl_engine* e, const rl_batch* device_batch, const int32_t* d_delta, uint32_t flags,
+                        rl_peek_reply* d_reply_or_null);
+int rl_adjust_submit(rl_engine* e, const rl_batch* host_batch, const int32_t* delta, uint32_t flags,
+                     int want_replies);
+int rl_wait_adjust(rl_engine* e, rl_peek_reply* out_or_null, rl_adjust_report* report_or_null);
 
 /* ---- Routed peek / forget --------------------------------------------------
  * The same lookups where the keys are spread over the shards of a router.
