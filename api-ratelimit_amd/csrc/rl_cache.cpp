@@ -189,6 +189,8 @@ struct HipRateLimitCache::Staged {
   bool failed = false;      // refused at submit: its callers already have the error
   uint64_t seq = 0;         // gathered (and submitted) in this order
   bool adjust = false;      // an rl_adjust_submit flight of queued adjusts (calls, nd and failed only)
+  bool refund = false;      // the rl_refund_behind flight of the decision batch in front of it (adjust is
+                            // set too: it claims nothing and is no decision; no calls wait on it)
 };
 
 // The queued adjusts of one gather with one keep flag: one rl_batch in plain memory, one request
@@ -687,6 +689,7 @@ static int64_t compact_base(int64_t first_now) { return first_now > 0 ? first_no
 // A call the compact form can carry: prefixes of at most 65535 bytes, hits_addend below 2^24 and
 // rule ids (those it has and those it would be given) below 0xFFFF.
 bool HipRateLimitCache::compactable(const PendingCall& c) const {
+  if (s_.refund_rejected) return false;  // a refund reads statuses on the device: a compact batch leaves none there
   if (c.req->HitsAddend > 0xFFFFFFu) return false;
   size_t fresh = 0;
   for (size_t i = 0; i < c.prefix.size(); ++i) {
@@ -844,6 +847,11 @@ void HipRateLimitCache::submit(Staged& st, std::deque<Staged>& inflight) {
 // memory (no copy), read here before the next submit reuses the slot.
 void HipRateLimitCache::finish(Staged& st) {
   if (st.failed) return;
+  if (st.refund) {
+    // (nobody waits for it; a failed refund wrote nothing, and its batch's answers stand)
+    if (rl_wait_refund(eng_, nullptr)) n_refund_fail_ += 1;
+    return;
+  }
   if (st.adjust) {
     // nothing was applied when the flight fails: every call of it gets the error
     adj_rep_.resize(st.nd ? st.nd : 1u);
@@ -1072,7 +1080,24 @@ void HipRateLimitCache::submitter() {
     const uint64_t seq = st.seq;
     if (!st.calls.empty()) {
       submit(st, inflight);
+      const bool decided = !st.failed;
       inflight.push_back(std::move(st));
+      // HIP_REFUND_REJECTED: the batch's rejected requests get their hits back, right behind it and
+      // in front of the gather's adjusts. Completing older flights for room never reaches the batch
+      // itself: it is the newest of at most RL_MAX_IN_FLIGHT.
+      if (s_.refund_rejected && decided) {
+        while (inflight.size() >= RL_MAX_IN_FLIGHT) finish_oldest(inflight);
+        Staged rf;
+        rf.adjust = rf.refund = true;
+        rf.seq = seq;
+        // HIP_LOCAL_CACHE=freecache: the device cache is unused, as in Adjust
+        if (rl_refund_behind(eng_, fc_ ? (uint32_t)RL_REFUND_KEEP_CACHE : 0u)) {
+          n_refund_fail_ += 1;  // (the engine refused it: the batch stays charged as the reference charges it)
+        } else {
+          n_refunds_ += 1;
+          inflight.push_back(std::move(rf));
+        }
+      }
     }
     for (int k = 0; k < 2; ++k) {
       if (ag[k].calls.empty()) continue;

@@ -185,6 +185,11 @@ struct HipSettings {
   // (HIP_TABLE_MAX_SLOTS). HipRateLimitCache::Resize below.
   uint32_t autogrow_permille = 0;
   uint32_t max_log2_slots[4] = {31, 31, 31, 31};
+  // HIP_REFUND_REJECTED (off by default; an extension, rl_hip.h "Refund"): every decision batch is
+  // followed by one rl_refund_behind flight, so a request the limiter rejects gives back what its
+  // descriptors were charged. The statuses must stay on the device for it, so the batcher then
+  // sends every batch in the full format, never the compact one.
+  bool refund_rejected = false;
   bool answer_early = true;                // HIP_BATCH_ANSWER_EARLY: while gathering, answer the batch in
                                            // flight as soon as the device is done with it (rl_query)
   // EXPIRATION_JITTER_MAX_SECONDS (settings.go:43, default 300; at most 65536 here): every INCRBY's
@@ -351,6 +356,10 @@ class HipRateLimitCache : public RateLimitCache {
     return {n_batches_.load(), n_loads_.load(),   n_loads_inflight_.load(), n_drains_.load(),
             n_compact_.load(), n_resizes_.load(), n_resize_fail_.load()};
   }
+  // HIP_REFUND_REJECTED: refund flights made, and those the engine refused or that failed (such a
+  // batch stays charged as the reference charges it).
+  uint64_t refund_flights() const { return n_refunds_.load(); }
+  uint64_t refund_failures() const { return n_refund_fail_.load(); }
   // (tests) set before the first DoLimit
   void set_trace(TraceFn f) { trace_ = std::move(f); }
   // The ratelimit.localcache.* gauges: hits, misses, lookups, entries, evicted,
@@ -400,6 +409,7 @@ class HipRateLimitCache : public RateLimitCache {
   std::vector<rl_rule> rules_;
   bool rules_dirty_ = false;
   std::atomic<uint64_t> n_batches_{0}, n_loads_{0}, n_loads_inflight_{0}, n_drains_{0}, n_compact_{0};
+  std::atomic<uint64_t> n_refunds_{0}, n_refund_fail_{0};  // HIP_REFUND_REJECTED: flights made; refused or failed
   std::atomic<uint64_t> n_resizes_{0}, n_resize_fail_{0};
   std::atomic<uint64_t> lc_lookups_{0}, lc_hits_{0};  // the device cache's Gets and hits (finish())
   uint32_t grow_failed_at_[4] = {0, 0, 0, 0};  // live slots of the unit when its last grow failed (0 = none)

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "rl_adjust.h"
+#include "rl_refund.h"
 #include "rl_census.h"
 #include "rl_common.h"
 #include "rl_hip.h"
@@ -93,7 +94,7 @@ enum KernelId {
   KT_FINGERPRINT, KT_HISTOGRAM, KT_HIST_SCAN, KT_SORT_PASS, KT_SCAN, KT_LEADER, KT_DECIDE, KT_FALLBACK, KT_MEMSET,
   KT_CAND, KT_V4_HIST, KT_V4_SCAN, KT_V4_PLACE, KT_V4_GROUP, KT_RESOLVE, KT_RULE_STATS, KT_CACHE_STATS, KT_CENSUS,
   KT_SET_INDEX, KT_SET_PLAN, KT_SET_APPLY, KT_SET_INDEX_ROUTED, KT_MERGE_PLAN, KT_MERGE_APPLY,
-  KT_ADJUST_INDEX, KT_ADJUST_APPLY, KT_ADJUST_INDEX_ROUTED, KT_ADJUST_PACK, KT_COUNT
+  KT_ADJUST_INDEX, KT_ADJUST_APPLY, KT_ADJUST_INDEX_ROUTED, KT_ADJUST_PACK, KT_REFUND_MARK, KT_REFUND_INDEX, KT_COUNT
 };
 const char* const kKernelNames[KT_COUNT] = {"k_fingerprint", "k_histogram", "k_hist_scan", "k_sort_pass", "k_scan",
                                             "k_leader",      "k_decide",    "fallback",    "memset",      "k_cand_state",
@@ -101,7 +102,8 @@ const char* const kKernelNames[KT_COUNT] = {"k_fingerprint", "k_histogram", "k_h
                                             "k_resolve",     "k_rule_stats", "k_cache_stats", "k_census",
                                             "k_set_index",   "k_set_plan",  "k_set_apply", "k_set_index_routed",
                                             "k_merge_plan",  "k_merge_apply", "k_adjust_index", "k_adjust_apply",
-                                            "k_adjust_index_routed", "k_adjust_pack"};
+                                            "k_adjust_index_routed", "k_adjust_pack", "k_refund_mark",
+                                            "k_refund_index"};
 
 enum Mode { MODE_LSD = 1, MODE_LSD_FULL = 2, MODE_V4 = 4 };
 
@@ -194,10 +196,25 @@ struct rl_engine {
   // pinned copy of the flight's control block, fetched on the stream behind its applying pass, and
   // for the host form pinned and device staging of the deltas (4 B x max_batch_desc each). Allocated
   // at the first call that needs them and kept.
+  // (the pinned copy has a refund's size, RefCtl: an adjust's block and one line more)
   AdjCtl* h_adj_ctl[RL_MAX_IN_FLIGHT] = {};
   int32_t* h_adj_delta[RL_MAX_IN_FLIGHT] = {};
   int32_t* d_adj_delta[RL_MAX_IN_FLIGHT] = {};
   int adj_flight_ensure(bool host);
+  // A refund in flight (rl_hip.h "Refund") is an adjust flight with kernels of its own in front of
+  // the applying pass. rej: one word per request (4 B x max_batch_req), allocated at the first
+  // refund and kept. stage_hold[s]: the completion event of a refund that reads host slot s's
+  // staged inputs and device statuses (rl_refund_behind of a host batch); the slot's next H2D copy
+  // waits for it on the copy-in stream.
+  uint32_t* d_ref_rej = nullptr;
+  hipEvent_t stage_hold[RL_MAX_IN_FLIGHT] = {};
+  hipEvent_t ev_hold[RL_MAX_IN_FLIGHT] = {};  // the holds' own events (a slot's done_ev is recorded again too soon)
+  int refund_ensure();
+  void stage_release(uint32_t s) {
+    if (!stage_hold[s]) return;
+    hipStreamWaitEvent(xin, stage_hold[s], 0);
+    stage_hold[s] = nullptr;
+  }
   // The plan between rl_set_routed_plan / rl_adjust_routed_plan and its commit. Its index and its
   // control block stay in rl_set's scratch, so while one is open the engine refuses what an open
   // restore refuses (quiet, set_busy).
@@ -438,6 +455,15 @@ struct rl_engine {
     const int32_t* adj_delta = nullptr;  // device
     rl_peek_reply* adj_rep = nullptr;    // device, or null
     bool adj_clear = false;              // the call's cache part is on
+    // a refund flight (adjust is set too: it settles, chains and completes as an adjust does)
+    bool refund = false;
+    const rl_status* ref_st = nullptr;   // device: the refunded batch's statuses
+    uint32_t* ref_amount = nullptr;      // device, or null
+    // the statuses are those of the flight submitted just ahead (rl_refund_behind, or
+    // rl_refund_pipelined given that flight's status array): the kernels read that batch's error word
+    bool ref_tied = false;
+    bool ref_lsd = false;                // ... which is the LSD block's: the batch was rerun there already
+    uint64_t ref_bseq = 0;               // ... else v4_ctl[ref_bseq % 3]'s
   };
   Flight fl[HSLOTS];
   // A device v4 batch completes on the word k4_group's last block writes behind the slot's pinned
@@ -564,7 +590,8 @@ struct rl_engine {
   void update_hot(const HotCand* cand, uint32_t n_cand);
   int settle(Flight& f);
   int finish(rl_status* out, uint32_t* thr, bool into, rl_peek_reply* adj_out = nullptr,
-             rl_adjust_report* adj_report = nullptr);
+             rl_adjust_report* adj_report = nullptr, rl_refund_report* ref_report = nullptr);
+  int refund_submit(const rl_batch& d, const rl_status* d_status, uint32_t flags, uint32_t* d_amount, int tied);
   int adjust_queue(const Flight& f);
   int adjust_settle(Flight& f);
   int adjust_submit(const rl_batch& d, const int32_t* d_delta, uint32_t flags, rl_peek_reply* d_rep, bool host);
@@ -996,7 +1023,7 @@ static void adjust_report(const AdjCtl* hc, rl_adjust_report& rep);  // (with rl
 // stats and the host-path copy. A refused batch poisons the batch behind it (k4_place ->
 // k4_scan), so that one is settled here too, before anything else can be submitted.
 int rl_engine::finish(rl_status* out_into, uint32_t* thr_into, bool into, rl_peek_reply* adj_out,
-                      rl_adjust_report* adj_report) {
+                      rl_adjust_report* adj_report, rl_refund_report* ref_report) {
   Flight f = fl[0];
   for (int q = 1; q < n_fl; ++q) fl[q - 1] = fl[q];
   --n_fl;
@@ -1025,6 +1052,28 @@ int rl_engine::finish(rl_status* out_into, uint32_t* thr_into, bool into, rl_pee
     hipError_t e = hipStreamSynchronize(stream);  // the next batch's marks too
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
     fold_marks();
+  }
+  if (f.refund) {  // an adjust's end, in a refund's words
+    if (errs & ADJ_ERR_BADREC)
+      return fail(RL_EINVAL, "refund in flight: a descriptor with an unknown rule id or request index, malformed "
+                             "prefix offsets / request order, or a time outside [0, 0xFFFD0000] (nothing written)");
+    if (errs & ADJ_ERR_INDEX) return fail(RL_EDEVICE, "refund in flight: the call's index overflowed (nothing written)");
+    if (errs & ADJ_ERR_POISON) return fail(RL_EDEVICE, "refund in flight: refused again behind its batch's rerun");
+    if (errs & ADJ_ERR_BATCH)
+      return fail(RL_ESTATE, "refund in flight: the refunded batch failed on the device and wrote no statuses "
+                             "(nothing written)");
+    if (ref_report) {
+      const RefCtl* hc = reinterpret_cast<const RefCtl*>(h_adj_ctl[f.slot]);
+      memset(ref_report, 0, sizeof *ref_report);
+      ref_report->descriptors = f.b.n_desc;
+      ref_report->rejected_req = hc->rejected[0];
+      ref_report->skipped = hc->a.w[ADJ_NIL][0];
+      ref_report->absent = hc->a.w[ADJ_ABSENT][0];
+      ref_report->refunded = hc->a.w[ADJ_APPLIED][0];
+      ref_report->floored = hc->a.w[ADJ_FLOORED][0];
+      ref_report->unfrozen = hc->a.w[ADJ_UNFROZEN][0];
+    }
+    return 0;
   }
   if (f.adjust) {  // nothing was claimed: no hot-set, occupancy or stats work behind it
     if (errs & ADJ_ERR_BADREC)
@@ -1406,6 +1455,9 @@ void rl_destroy(rl_engine* e) {
     hipHostFree(e->h_adj_delta[k]);
     hipFree(e->d_adj_delta[k]);
   }
+  hipFree(e->d_ref_rej);
+  for (hipEvent_t ev : e->ev_hold)
+    if (ev) hipEventDestroy(ev);
   for (auto& g : e->stage) {
     hipFree(g.d_cin);
     hipFree(g.d_csum);
@@ -1550,6 +1602,7 @@ int rl_submit(rl_engine* e, const rl_batch* b, rl_status* out, uint32_t* req_thr
     if (a.n && a.src != h + a.o) memcpy(h + a.o, a.src, a.n);
   memset(h + b->blob_bytes, 0, RL_BLOB_SLACK);  // the device reads prefixes in 16-B words
   e->acquired = -1;
+  e->stage_release(s);  // a refund in flight may still read the slot's previous batch (rl_refund_behind)
   hipError_t he = hipSuccess;
   // Copy only the used extents of each array, on the copy-in stream: the previous batch's
   // kernels keep running meanwhile. prefix_off / rule_id / req_of (one pitch apart) move as one
@@ -1679,6 +1732,7 @@ int rl_submit_c(rl_engine* e, const rl_batch_c* b) {
     if (a.n && a.src != h + a.o) memcpy(h + a.o, a.src, a.n);
   memset(h + b->blob_bytes, 0, RL_BLOB_SLACK);  // the device reads prefixes in 16-B words
   e->acquired = -1;
+  e->stage_release(s);  // (rl_submit)
   // Two copies at one descriptor per request: the blob, and the desc and req words as one
   // 2-D copy (rows P apart); req_of, when present, is a third.
   hipError_t he = hipMemcpyAsync(g.d_in, h, (size_t)b->blob_bytes + RL_BLOB_SLACK, hipMemcpyHostToDevice, e->xin);
@@ -2938,7 +2992,7 @@ int rl_engine::adj_flight_ensure(bool host) {
   const size_t n = cfg.max_batch_desc ? cfg.max_batch_desc : 1u;
   hipError_t he = hipSuccess;
   for (int k = 0; k < HSLOTS && he == hipSuccess; ++k) {
-    if (!h_adj_ctl[k]) he = hipHostMalloc(&h_adj_ctl[k], sizeof(AdjCtl), hipHostMallocDefault);
+    if (!h_adj_ctl[k]) he = hipHostMalloc(&h_adj_ctl[k], sizeof(RefCtl), hipHostMallocDefault);
     if (he == hipSuccess && host && !h_adj_delta[k])
       he = hipHostMalloc(&h_adj_delta[k], n * sizeof(int32_t), hipHostMallocDefault);
     if (he == hipSuccess && host && !d_adj_delta[k]) he = hipMalloc(&d_adj_delta[k], n * sizeof(int32_t));
@@ -2954,10 +3008,44 @@ int rl_engine::adjust_queue(const Flight& f) {
   AdjCtl* hc = h_adj_ctl[f.slot];
   const uint32_t n = f.b.n_desc;
   if (!n) {  // (the slot's previous flight is complete: nothing is still copying into hc)
-    memset(hc, 0, sizeof(AdjCtl));
+    memset(hc, 0, sizeof(RefCtl));
     return 0;
   }
   const AdjScratch sc = adj_view(n);
+  if (f.refund) {
+    // rej and the control block zeroed, the marking pass, the index zeroed, the index kernel, the
+    // applying pass, the copy of the control block
+    hipError_t he = hipMemsetAsync(d_ref_rej, 0, (size_t)f.b.n_req * 4, stream);
+    if (he == hipSuccess) he = hipMemsetAsync(sc.ctl, 0, sizeof(RefCtl), stream);
+    if (he != hipSuccess) return hip_fail(he, "refund in flight (nothing written)");
+    // The refunded batch's error word: its v4 block, which this flight clears (in k4_group's place)
+    // only behind its kernels; once the batch has been rerun (this is the refund's own rerun, or the
+    // batch was rerun before the refund was submitted), the LSD block, which the rerun left last.
+    const uint32_t* berr = !f.ref_tied ? nullptr
+                           : (f.fell_back || f.ref_lsd) ? &reinterpret_cast<const EngineCtl*>(zero_block)->err
+                                                        : &v4_ctl[f.ref_bseq % 3]->err;
+    auto run = [&](int pass) {
+      launch_refund_flight(stream, f.b, f.ref_st, d_rules, n_rules, cfg.hash_seed, tab, d_ref_rej, f.ref_amount, sc,
+                           d_poison, berr, pass);
+    };
+    timed(KT_REFUND_MARK, [&] { run(0); });
+    he = hipGetLastError();
+    // (the control block is zeroed once, in front of the marking pass: behind a refused batch all
+    // three kernels set the same poison bit in it)
+    if (he == hipSuccess) he = hipMemsetAsync(sc.index, 0, sizeof(AdjEntry) << sc.log2_entries, stream);
+    if (he != hipSuccess) return hip_fail(he, "refund in flight (nothing written)");
+    timed(KT_REFUND_INDEX, [&] { run(1); });
+    he = hipGetLastError();
+    if (he != hipSuccess) return hip_fail(he, "refund in flight (nothing written)");
+    timed(KT_ADJUST_APPLY, [&] {
+      launch_adjust_flight(stream, f.b, d_rules, n_rules, cfg.hash_seed, tab, nullptr, nullptr, f.adj_clear, sc,
+                           d_poison, 1);
+    });
+    he = hipGetLastError();
+    if (he == hipSuccess) he = hipMemcpyAsync(hc, sc.ctl, sizeof(RefCtl), hipMemcpyDeviceToHost, stream);
+    if (he != hipSuccess) return hip_fail(he, (std::string("refund in flight") + kApplyFailed).c_str());
+    return 0;
+  }
   hipError_t he = adjust_index_run(sc, KT_ADJUST_INDEX, [&] {
     launch_adjust_flight(stream, f.b, d_rules, n_rules, cfg.hash_seed, tab, f.adj_delta, f.adj_rep, f.adj_clear, sc,
                          d_poison, 0);
@@ -3093,7 +3181,122 @@ int rl_wait_adjust(rl_engine* e, rl_peek_reply* out_or_null, rl_adjust_report* r
   if (!e) return RL_EINVAL;
   if (!e->n_fl) return e->fail(RL_ESTATE, "rl_wait_adjust without a flight in flight");
   if (!e->fl[0].adjust) return e->fail(RL_ESTATE, "rl_wait_adjust: the oldest flight is a batch (rl_wait)");
+  if (e->fl[0].refund) return e->fail(RL_ESTATE, "rl_wait_adjust: the oldest flight is a refund (rl_wait_refund)");
   return e->finish(nullptr, nullptr, false, out_or_null, report_or_null);
+}
+
+// ---- Refund -----------------------------------------------------------------------------------
+// rl_refund_pipelined / rl_refund_behind / rl_wait_refund (rl_hip.h "Refund"). A
+// refund is an adjust flight whose deltas are made on the device: adjust_queue runs its kernels
+// (and runs them all again behind a refused batch's rerun), adjust_settle and finish treat it as
+// the adjust it is, and only its two waits differ.
+
+int rl_engine::refund_ensure() {
+  if (int rc = adj_flight_ensure(false)) return rc;
+  if (d_ref_rej) return 0;
+  const size_t n = cfg.max_batch_req ? cfg.max_batch_req : 1u;
+  hipError_t he = hipMalloc(&d_ref_rej, n * 4);
+  for (int k = 0; k < HSLOTS && he == hipSuccess; ++k)
+    if (!ev_hold[k]) he = hipEventCreateWithFlags(&ev_hold[k], hipEventDisableTiming);
+  if (he == hipSuccess) return 0;
+  if (d_ref_rej) hipFree(d_ref_rej);
+  d_ref_rej = nullptr;
+  (void)hipGetLastError();
+  return hip_fail(he, "refund scratch allocation");
+}
+
+// tied: -1, or the index in fl of the flight whose statuses these are (the newest)
+int rl_engine::refund_submit(const rl_batch& d, const rl_status* d_status, uint32_t flags, uint32_t* d_amount,
+                             int tied) {
+  if (resolve_pending) {  // rule ids from an rl_resolve_device on the front stream
+    const hipError_t we = hipStreamWaitEvent(stream, ev_resolve, 0);
+    if (we != hipSuccess) return hip_fail(we, "hipStreamWaitEvent(resolve)");
+    resolve_pending = false;
+  }
+  const uint32_t s = (uint32_t)(sub_seq % HSLOTS);
+  Flight f;
+  f.adjust = true;
+  f.refund = true;
+  f.b = d;
+  f.ref_st = d_status;
+  f.ref_amount = d_amount;
+  if (tied >= 0) {
+    f.ref_tied = true;
+    f.ref_lsd = fl[tied].fell_back;
+    f.ref_bseq = sub_seq - 1;
+  }
+  f.adj_clear = tab.local_cache && !(flags & RL_REFUND_KEEP_CACHE);
+  f.slot = s;
+  int rc = adjust_queue(f);
+  if (rc) return rc;
+  // k4_group of a batch clears the control block of the batch two behind it; in its place:
+  hipError_t e = hipMemsetAsync(v4_ctl[(sub_seq + 2) % 3], 0, sizeof(EngineCtl), stream);
+  done_ev[s] = ev_done[s];
+  if (e == hipSuccess) e = hipEventRecord(done_ev[s], stream);
+  if (e != hipSuccess) return hip_fail(e, "hipEventRecord(done)");
+  fl[n_fl++] = f;
+  ++sub_seq;
+  return 0;
+}
+
+// What both refund calls check: rl_adjust_pipelined's gates in its order, then the arrays.
+static int refund_enter(rl_engine* e, const rl_batch* b, const rl_status* d_status, uint32_t flags, const char* what) {
+  if (e->n_fl >= HSLOTS) return e->fail(RL_ESTATE, "%s with %d flights in flight (call rl_wait)", what, HSLOTS);
+  if (e->restoring) return e->fail(RL_ESTATE, "%s between rl_restore_begin and rl_restore_end", what);
+  if (int rc = e->set_busy(what)) return rc;
+  if (int rc = peek_args(e, b, what, false)) return rc;
+  if (e->cfg.max_batch_desc > SET_MAX_DESC)
+    return e->fail(RL_ECAPACITY, "%s: max_batch_desc %u above 2^29", what, e->cfg.max_batch_desc);
+  if (b->n_desc && !d_status) return e->fail(RL_EINVAL, "%s: null status array", what);
+  if (b->n_req && !b->hits_addend) return e->fail(RL_EINVAL, "%s: null hits_addend", what);
+  if (flags & ~(uint32_t)RL_REFUND_KEEP_CACHE) return e->fail(RL_EINVAL, "%s: unknown flag bits 0x%x", what, flags);
+  if (e->n_fl && e->default_mode() != MODE_V4)
+    return e->fail(RL_ESTATE, "%s: a refund behind another flight needs the v4 pipeline (call rl_wait)", what);
+  return 0;
+}
+
+int rl_refund_pipelined(rl_engine* e, const rl_batch* b, const rl_status* d_status, uint32_t flags,
+                        uint32_t* d_amount_or_null) {
+  if (!e || !b) return RL_EINVAL;
+  int rc = refund_enter(e, b, d_status, flags, "rl_refund_pipelined");
+  if (rc) return rc;
+  if ((rc = e->refund_ensure()) != 0) return rc;
+  // statuses of the flight just ahead: that batch may yet fail, so its error word is read
+  const int last = e->n_fl - 1;
+  const bool tied = last >= 0 && !e->fl[last].adjust && !e->fl[last].raw && e->fl[last].out == d_status;
+  return e->refund_submit(*b, d_status, flags, d_amount_or_null, tied ? last : -1);
+}
+
+int rl_refund_behind(rl_engine* e, uint32_t flags) {
+  if (!e) return RL_EINVAL;
+  const char* what = "rl_refund_behind";
+  if (!e->n_fl) return e->fail(RL_ESTATE, "%s without a flight in flight", what);
+  const rl_engine::Flight g = e->fl[e->n_fl - 1];
+  if (g.adjust)
+    return e->fail(RL_ESTATE, "%s: the newest flight is %s, not a decision batch", what, g.refund ? "a refund" : "an adjust");
+  if (g.raw || g.reply || g.b.reserved || !g.out)
+    return e->fail(RL_ESTATE, "%s: the newest flight is a compact or routed batch (no statuses on the device)", what);
+  int rc = refund_enter(e, &g.b, g.out, flags, what);
+  if (rc) return rc;
+  if ((rc = e->refund_ensure()) != 0) return rc;
+  if ((rc = e->refund_submit(g.b, g.out, flags, nullptr, e->n_fl - 1)) != 0) return rc;
+  // A host batch's arrays and statuses are its slot's: the slot's next copy-in waits for this flight,
+  // on an event of the hold's own (the refund's done_ev is recorded again by the flight that takes
+  // its slot, before the held slot comes round)
+  if (g.host) {
+    const hipError_t he = hipEventRecord(e->ev_hold[g.slot], e->stream);
+    if (he != hipSuccess) return e->hip_fail(he, "hipEventRecord(hold)");
+    e->stage_hold[g.slot] = e->ev_hold[g.slot];
+  }
+  return 0;
+}
+
+int rl_wait_refund(rl_engine* e, rl_refund_report* report_or_null) {
+  if (!e) return RL_EINVAL;
+  if (!e->n_fl) return e->fail(RL_ESTATE, "rl_wait_refund without a flight in flight");
+  if (!e->fl[0].refund)
+    return e->fail(RL_ESTATE, "rl_wait_refund: the oldest flight is %s", e->fl[0].adjust ? "an adjust (rl_wait_adjust)" : "a batch (rl_wait)");
+  return e->finish(nullptr, nullptr, false, nullptr, nullptr, report_or_null);
 }
 
 // Routed adjust, the engine's pieces (rl_hip.h "Routed adjust"). The plan is rl_adjust up to and

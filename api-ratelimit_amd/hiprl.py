@@ -128,6 +128,14 @@ class RlAdjustReport(C.Structure):  # rl_adjust_report, 64 B
     _fields_ = [(f, C.c_uint64) for f in ADJUST_REPORT_FIELDS] + [("reserved", C.c_uint64)]
 
 
+REFUND_KEEP_CACHE = 1  # RL_REFUND_KEEP_CACHE: rl_refund_* leaves every local-cache deadline as it is
+REFUND_REPORT_FIELDS = ("descriptors", "rejected_req", "skipped", "absent", "refunded", "floored", "unfrozen")
+
+
+class RlRefundReport(C.Structure):  # rl_refund_report, 64 B
+    _fields_ = [(f, C.c_uint64) for f in REFUND_REPORT_FIELDS] + [("reserved", C.c_uint64)]
+
+
 # ---- rule stats (rl_hip.h "Rule stats") ----
 RULE_STATS_CLEAR = 1  # RL_RULE_STATS_CLEAR
 RULE_STAT_FIELDS = ("total_hits", "over_limit", "near_limit", "over_limit_with_local_cache", "shadow_mode")
@@ -315,6 +323,9 @@ ABI = [
     ("rl_adjust_pipelined", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_uint32, C.c_void_p], C.c_int),
     ("rl_adjust_submit", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_uint32, C.c_int], C.c_int),
     ("rl_wait_adjust", [C.c_void_p, C.c_void_p, C.POINTER(RlAdjustReport)], C.c_int),
+    ("rl_refund_pipelined", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_uint32, C.c_void_p], C.c_int),
+    ("rl_refund_behind", [C.c_void_p, C.c_uint32], C.c_int),
+    ("rl_wait_refund", [C.c_void_p, C.POINTER(RlRefundReport)], C.c_int),
     ("rl_peek_routed", [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32], C.c_int),
     ("rl_route_unpack_peek", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     ("rl_router_peek", [C.c_void_p, C.POINTER(RlBatch), C.POINTER(C.c_void_p)], C.c_int),
@@ -893,6 +904,32 @@ class Engine:
         n = int(rep.descriptors)
         out = buf[:n].copy() if n and buf["flags"][0] != 0xFFFFFFFF else None
         return out, {f: int(getattr(rep, f)) for f in ADJUST_REPORT_FIELDS}
+
+    # ---- refund (rl_hip.h "Refund") ----
+    def refund_pipelined(self, n_desc: int, n_req: int, blob_bytes: int, ptrs, status_ptr: int,
+                         keep_cache: bool = False, amount_ptr: int = 0):
+        """rl_refund_pipelined: the hits of the rejected requests of a decided batch given back, as a
+        flight. ptrs = the batch's device pointers (blob, off, rule, req_of, now, hits), status_ptr its
+        n_desc statuses in device memory; the amount per descriptor (uint32, 0: skipped) goes to device
+        memory at amount_ptr unless 0. wait_refund() (or wait()) completes it."""
+        s = RlBatch()
+        s.n_desc, s.n_req, s.blob_bytes, s.reserved = n_desc, n_req, blob_bytes, 0
+        _set_ptrs(s, ptrs)
+        self._check(self.lib.rl_refund_pipelined(self.h, C.byref(s), status_ptr or None,
+                                                 REFUND_KEEP_CACHE if keep_cache else 0, amount_ptr or None),
+                    "rl_refund_pipelined")
+
+    def refund_behind(self, keep_cache: bool = False):
+        """rl_refund_behind: refund_pipelined of the most recently submitted flight (a decision batch
+        with statuses, still in flight), from that flight's own device arrays."""
+        self._check(self.lib.rl_refund_behind(self.h, REFUND_KEEP_CACHE if keep_cache else 0), "rl_refund_behind")
+
+    def wait_refund(self) -> dict:
+        """rl_wait_refund: complete the oldest flight, which must be a refund. Returns the report as a
+        dict of REFUND_REPORT_FIELDS."""
+        rep = RlRefundReport()
+        self._check(self.lib.rl_wait_refund(self.h, C.byref(rep)), "rl_wait_refund")
+        return {f: int(getattr(rep, f)) for f in REFUND_REPORT_FIELDS}
 
     def peek_device(self, n_desc: int, n_req: int, blob_bytes: int, ptrs, out_ptr: int):
         """rl_peek_device: an rl_batch of device pointers (ptrs = blob, off, rule, req_of, now, hits

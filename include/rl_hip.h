@@ -1003,6 +1003,81 @@ int rl_adjust_submit(rl_engine* e, const rl_batch* host_batch, const int32_t* de
                      int want_replies);
 int rl_wait_adjust(rl_engine* e, rl_peek_reply* out_or_null, rl_adjust_report* report_or_null);
 
+/* ---- Refund -------------------------------------------------------------------
+ * Gives a rejected request's hits back, on the device. An extension, opt-in per call: the reference
+ * issues INCRBY for every descriptor that is not a local-cache hit, whatever the verdict
+ * (fixed_cache_impl.go:60-80), and only ORs the codes afterwards (ratelimit.go:208-215), so a request
+ * it rejects is still charged on every one of its descriptors. For a cost limiter (hits_addend as
+ * tokens, bytes, credits) that is the largest source of wrong charges: a request of cost 1500 that
+ * meets a counter at 9000 / 10000 leaves it at 10500, and a request of cost 100 behind it is refused
+ * although 1000 units remain; a request rejected by its global descriptor has still spent its
+ * per-user descriptor's quota. Everything the correction needs is in device memory when the batch
+ * ends (the statuses, req_of, hits_addend, the key prefixes), so no status is read back.
+ *
+ * Which descriptors are owed: a request is rejected when any of its descriptors has code
+ * RL_CODE_OVER_LIMIT in d_status (a shadowed descriptor is RL_CODE_OK with RL_FLAG_SHADOW and rejects
+ * nothing). A descriptor of a rejected request is owed max(1, hits_addend[req_of[i]]), the over-limit
+ * descriptor itself included (it was counted), unless its rule is RL_NIL_RULE or its status carries
+ * RL_FLAG_LOCAL_CACHE_HIT: no INCRBY happened for those. Every other descriptor is skipped: no
+ * lookup is made for it. The amount is the full uint32 and is summed in 64 bits: it never passes
+ * through an int32 delta, so hits_addend of 2^31 and 2^32 - 1 refund exactly. d_amount_or_null
+ * (n_desc words of device memory) receives the amount per descriptor, 0 for a skipped one.
+ *
+ * What is written: rl_adjust's rules ("Adjust" above), word for word, with net = -(the sum of the
+ * amounts over the call's found descriptors of a (string, store) pair): identity, store and "found"
+ * at the descriptor's own request time; nothing is ever claimed; the result is clamped at 0; the
+ * expiry is untouched; each pair is written once. The cache part is rl_adjust's, RL_REFUND_KEEP_CACHE
+ * is RL_ADJUST_KEEP_CACHE: a pair with new <= its smallest limit gets its string's local-cache
+ * deadline cleared, so a key a rejected request froze and the refund brought back under its limit
+ * counts again. Untouched, as for an adjust: rule stats, cache stats, rl_engine_stats, occupancy,
+ * the hot set and the candidate stash. The statuses of the refunded batch are not rewritten: the
+ * answer stays the reference's. The refund is after the fact, not an atomic multi-descriptor
+ * decision: later descriptors of the same batch were decided on the counters before it.
+ *
+ * rl_refund_pipelined: the batch's arrays (hits_addend included; ttl_jitter is not read), d_status
+ * (n_desc statuses) and d_amount are device memory; the caller leaves them alone until the flight's
+ * wait has returned. rl_refund_behind: refunds the most recently submitted flight, which must be a
+ * decision batch with statuses on the device (rl_submit, rl_submit_device, rl_submit_pipelined) and
+ * still be in flight; it reads that flight's own device arrays and statuses, so a host batcher
+ * passes no pointer. RL_ESTATE when nothing is in flight or the newest flight is an adjust, a
+ * refund, a compact (rl_submit_c) or a routed batch. A host batch's staging slot is held for the
+ * refund: the slot's next copy-in is ordered behind the refund's kernels on the device.
+ *
+ * Flights: a refund is a flight exactly as an adjust is ("Adjust in flight" above): it counts
+ * towards RL_MAX_IN_FLIGHT, completes in submission order, runs on the engine stream, and the same
+ * RL_ESTATE gates apply (a restore or a routed plan open; behind another flight only with the v4
+ * pipeline). rl_wait completes it and drops the report; rl_query works on it. rl_wait_refund on
+ * anything else, and rl_wait_adjust, rl_wait_into, rl_wait_view and rl_wait_raw_* on a refund,
+ * return RL_ESTATE and complete nothing. Behind a batch the bucketed pipeline refused, every refund
+ * kernel finds the poison word, writes nothing, and the wait runs the whole refund again behind the
+ * batch's rerun, marking pass included: the statuses are final only then.
+ * A batch that fails on the device (RL_ENOSPC, a window span, RL_EDEVICE, bad input: its wait returns
+ * the error) wrote no statuses, and its status array still holds whatever an earlier batch left
+ * there. rl_refund_behind, and rl_refund_pipelined when d_status is the status array of the most
+ * recently submitted flight, read that batch's device error word first: behind a failed batch every
+ * refund kernel writes nothing and the refund's wait returns RL_ESTATE. rl_refund_pipelined with any
+ * other d_status cannot be tied to a batch: the caller passes only statuses of a batch whose wait
+ * has returned 0.
+ * Refused at once, no flight added: rl_adjust_pipelined's list, a null d_status or hits_addend, a
+ * flag bit other than RL_REFUND_KEEP_CACHE. A descriptor rl_peek_device would answer RL_PEEK_BAD
+ * makes the wait return RL_EINVAL with nothing written. n_desc == 0 is an empty flight with a zero
+ * report. Scratch: rl_set's, and 4 B x max_batch_req. */
+enum { RL_REFUND_KEEP_CACHE = 1u };
+typedef struct rl_refund_report {  /* 64 B */
+  uint64_t descriptors;   /* n_desc of the refunded batch */
+  uint64_t rejected_req;  /* requests with at least one descriptor of code RL_CODE_OVER_LIMIT */
+  uint64_t skipped;       /* descriptors that refund nothing: no lookup made */
+  uint64_t absent;        /* owed a refund, counter not found: nothing written */
+  uint64_t refunded;      /* owed a refund, counter found: amount entered its pair's sum */
+  uint64_t floored;       /* (string, store) pairs whose result stopped at 0 */
+  uint64_t unfrozen;      /* strings whose non-zero local-cache deadline was cleared */
+  uint64_t reserved;      /* 0 */
+} rl_refund_report;       /* descriptors == skipped + absent + refunded */
+int rl_refund_pipelined(rl_engine* e, const rl_batch* device_batch, const rl_status* d_status, uint32_t flags,
+                        uint32_t* d_amount_or_null);
+int rl_refund_behind(rl_engine* e, uint32_t flags);
+int rl_wait_refund(rl_engine* e, rl_refund_report* report_or_null);
+
 /* ---- Routed peek / forget --------------------------------------------------
  * The same lookups where the keys are spread over the shards of a router.
  *
