@@ -63,10 +63,16 @@ struct PendingCall {
   // HipRoutedRateLimitCache: a Peek (1), Forget (2), Set (3) or Adjust (4; 5 with keep_cache)
   // instead of a request, answered at a rule / stop agreement into `peek`; a Set's values (with its
   // KEEP bits or-ed in) in `set_vals`, an Adjust's deltas in `deltas`
+  // or, queued by the batcher itself with nobody waiting (HIP_REFUND_REJECTED), the refund of a
+  // rejected request (6; 7 with RL_REFUND_KEEP_CACHE): req and limits are null (the caller has been
+  // answered), the request's time and raw HitsAddend in `now` and `hits`, its agreed rule ids in
+  // `rule_ids` and its statuses in `statuses`
   int kind = 0;
   std::vector<PeekStatus> peek;
   std::vector<rl_peek_reply> set_vals;
   std::vector<int32_t> deltas;
+  std::vector<uint32_t> rule_ids;
+  std::vector<rl_status> statuses;
   // HipRateLimitCache::AdjustQueued: an adjust that waits in the queue like a DoLimit (prefix,
   // limits and deltas as above, answered into `peek`); keep: RL_ADJUST_KEEP_CACHE
   bool adj_queued = false, keep = false;
@@ -1124,11 +1130,12 @@ struct HipRoutedRateLimitCache::Step {
 
 namespace {
 // One rank's words in a rule / stop agreement (rl_router_allgather_host, RL_ROUTER_AG_MAX bytes).
-constexpr uint32_t SYNC_RULES = (RL_ROUTER_AG_MAX - 32) / sizeof(rl_rule);
+constexpr uint32_t SYNC_RULES = (RL_ROUTER_AG_MAX - 40) / sizeof(rl_rule);
 struct SyncWords {
   uint32_t stop, n;
   uint32_t n_peek, n_forget, n_set;  // pending Peek / Forget / Set calls of this rank
-  uint32_t n_adj, n_adj_keep, pad;   // pending Adjust calls without / with keep_cache
+  uint32_t n_adj, n_adj_keep;        // pending Adjust calls without / with keep_cache
+  uint32_t n_ref, n_ref_keep, pad;   // pending refunds of rejected requests without / with keep_cache
   rl_rule rules[SYNC_RULES];
 };
 static_assert(sizeof(SyncWords) <= RL_ROUTER_AG_MAX, "sync words");
@@ -1239,9 +1246,12 @@ bool HipRoutedRateLimitCache::known(const PendingCall& c) {
 // The rule / stop agreement (nothing in flight on any rank): every rank's new limits appended to
 // every rank's table in rank order (the first occurrence keeps its id), loaded into the engine.
 // Returns true when every rank asked to stop.
-// Then the control calls: if any rank has pending Peeks every rank makes one rl_router_peek, then
-// the same for Forgets, then for Sets (rl_router_set), then for Adjusts without keep_cache and for
-// Adjusts with it (rl_router_adjust: its flags word is per origin, hence the two calls).
+// Then the control calls: first the refunds of the requests the steps before rejected
+// (HIP_REFUND_REJECTED; rl_router_refund, without the keep bit and with it: its flags word is per
+// origin), so that every caller's control call of this agreement sees them; then, if any rank has
+// pending Peeks every rank makes one rl_router_peek, then the same for Forgets, then for Sets
+// (rl_router_set), then for Adjusts without keep_cache and for Adjusts with it (rl_router_adjust:
+// its flags word is per origin too, hence the two calls).
 bool HipRoutedRateLimitCache::sync(bool want_stop, std::deque<std::shared_ptr<PendingCall>>& ctl, uint64_t seq) {
   SyncWords mine;
   memset(&mine, 0, sizeof mine);
@@ -1251,7 +1261,9 @@ bool HipRoutedRateLimitCache::sync(bool want_stop, std::deque<std::shared_ptr<Pe
      : c->kind == 2 ? mine.n_forget
      : c->kind == 3 ? mine.n_set
      : c->kind == 4 ? mine.n_adj
-                    : mine.n_adj_keep) += 1;
+     : c->kind == 5 ? mine.n_adj_keep
+     : c->kind == 6 ? mine.n_ref
+                    : mine.n_ref_keep) += 1;
   mine.n = (uint32_t)std::min<size_t>(pending_.size(), SYNC_RULES);
   std::copy(pending_.begin(), pending_.begin() + mine.n, mine.rules);
   std::vector<SyncWords> all(r_.n_shards);
@@ -1259,6 +1271,7 @@ bool HipRoutedRateLimitCache::sync(bool want_stop, std::deque<std::shared_ptr<Pe
   if (rc) throw RedisError(std::string("rule agreement: ") + rl_router_last_error(rt_));
   n_syncs_ += 1;
   bool all_stop = true, any_peek = false, any_forget = false, any_set = false, any_adj = false, any_adj_keep = false;
+  bool any_ref = false, any_ref_keep = false;
   const size_t before = rules_.size();
   for (const SyncWords& w : all) {
     all_stop &= w.stop != 0;
@@ -1267,6 +1280,8 @@ bool HipRoutedRateLimitCache::sync(bool want_stop, std::deque<std::shared_ptr<Pe
     any_set |= w.n_set != 0;
     any_adj |= w.n_adj != 0;
     any_adj_keep |= w.n_adj_keep != 0;
+    any_ref |= w.n_ref != 0;
+    any_ref_keep |= w.n_ref_keep != 0;
     for (uint32_t i = 0; i < w.n; ++i) {
       const auto k = std::make_pair(w.rules[i].requests_per_unit, w.rules[i].unit);
       if (ids_.emplace(k, (uint32_t)rules_.size()).second) rules_.push_back(w.rules[i]);
@@ -1280,6 +1295,8 @@ bool HipRoutedRateLimitCache::sync(bool want_stop, std::deque<std::shared_ptr<Pe
     if (rc) throw RedisError(std::string("rl_load_rules: ") + rl_last_error(eng_));
     n_rules_ = rules_.size();
   }
+  if (any_ref) run_control(6, ctl, seq);
+  if (any_ref_keep) run_control(7, ctl, seq);
   if (any_peek) run_control(1, ctl, seq);
   if (any_forget) run_control(2, ctl, seq);
   if (any_set) run_control(3, ctl, seq);
@@ -1289,10 +1306,11 @@ bool HipRoutedRateLimitCache::sync(bool want_stop, std::deque<std::shared_ptr<Pe
 }
 
 // One collective rl_router_peek (kind 1) / rl_router_forget (kind 2) / rl_router_set (kind 3) /
-// rl_router_adjust (kind 4; kind 5 with RL_ADJUST_KEEP_CACHE) at an agreement: this rank's
-// pending calls of the kind whose limits are agreed, in enqueue order, as one request each, as far
-// as one router batch holds them (the others wait for the following agreement); an empty batch
-// when there are none.
+// rl_router_adjust (kind 4; kind 5 with RL_ADJUST_KEEP_CACHE) / rl_router_refund (kind 6; kind 7
+// with RL_REFUND_KEEP_CACHE) at an agreement: this rank's pending calls of the kind whose limits are
+// agreed, in enqueue order, as one request each, as far as one router batch holds them (the others
+// wait for the following agreement); an empty batch when there are none. A refund is a rejected
+// request as it was decided: its own time, rule ids, HitsAddend and statuses.
 void HipRoutedRateLimitCache::run_control(int kind, std::deque<std::shared_ptr<PendingCall>>& ctl, uint64_t seq) {
   std::vector<std::shared_ptr<PendingCall>> calls;
   std::vector<uint8_t> blob;
@@ -1300,10 +1318,13 @@ void HipRoutedRateLimitCache::run_control(int kind, std::deque<std::shared_ptr<P
   std::vector<int64_t> now;
   std::vector<rl_peek_reply> val;  // (a Set's)
   std::vector<int32_t> dl;         // (an Adjust's)
+  std::vector<uint32_t> hits;      // (a refund's)
+  std::vector<rl_status> sts;      // (a refund's)
+  const bool refund = kind == 6 || kind == 7;
   const size_t max_blob = (size_t)s_.batch_limit * 128u;
   for (auto it = ctl.begin(); it != ctl.end();) {
     PendingCall& c = **it;
-    if (c.kind != kind || !known(c)) {
+    if (c.kind != kind || (!refund && !known(c))) {  // (a refund's rule ids were agreed when it was decided)
       ++it;
       continue;
     }
@@ -1312,13 +1333,21 @@ void HipRoutedRateLimitCache::run_control(int kind, std::deque<std::shared_ptr<P
       break;  // (enqueue order: the rest of the kind waits too)
     if (trace_) trace_(c.req, seq, kTraceControl);
     const uint32_t rq = (uint32_t)now.size();
-    now.push_back(ts_->UnixNow());
+    now.push_back(refund ? c.now : ts_->UnixNow());
     for (size_t i = 0; i < c.prefix.size(); ++i) {
-      const auto& lim = (*c.limits)[i];
       blob.insert(blob.end(), c.prefix[i].begin(), c.prefix[i].end());
       off.push_back((uint32_t)blob.size());
-      rule.push_back(lim ? ids_.at(limit_key(*lim)) : RL_NIL_RULE);
+      if (refund) {
+        rule.push_back(c.rule_ids[i]);
+      } else {
+        const auto& lim = (*c.limits)[i];
+        rule.push_back(lim ? ids_.at(limit_key(*lim)) : RL_NIL_RULE);
+      }
       req_of.push_back(rq);
+    }
+    if (refund) {
+      hits.push_back(c.hits);
+      sts.insert(sts.end(), c.statuses.begin(), c.statuses.end());
     }
     val.insert(val.end(), c.set_vals.begin(), c.set_vals.end());
     dl.insert(dl.end(), c.deltas.begin(), c.deltas.end());
@@ -1341,15 +1370,26 @@ void HipRoutedRateLimitCache::run_control(int kind, std::deque<std::shared_ptr<P
   const rl_peek_reply* vals[1] = {val.data()};
   dl.resize(std::max<size_t>(1, dl.size()));
   const int32_t* dls[1] = {dl.data()};
-  const uint32_t flags[1] = {kind == 5 ? (uint32_t)RL_ADJUST_KEEP_CACHE : 0u};
+  const uint32_t flags[1] = {kind == 5 || kind == 7 ? (uint32_t)RL_ADJUST_KEEP_CACHE : 0u};
+  static_assert((uint32_t)RL_REFUND_KEEP_CACHE == (uint32_t)RL_ADJUST_KEEP_CACHE, "one keep bit");
+  hits.resize(std::max<size_t>(1, hits.size()));
+  sts.resize(std::max<size_t>(1, sts.size()));
+  b.hits_addend = refund ? hits.data() : nullptr;
+  const rl_status* stp[1] = {sts.data()};
   const int rc = kind == 1   ? rl_router_peek(rt_, &b, outs)
                  : kind == 2 ? rl_router_forget(rt_, &b, outs)
                  : kind == 3 ? rl_router_set(rt_, &b, vals, outs)
+                 : refund    ? rl_router_refund(rt_, &b, stp, flags, nullptr, nullptr, nullptr)
                              : rl_router_adjust(rt_, &b, dls, flags, outs, nullptr);
+  if (refund && !calls.empty()) (rc ? n_refund_fail_ : n_refunds_) += 1;
   if (rc) {
     const std::string msg = rl_router_last_error(rt_);
     fail(calls, msg);
     if (rc == RL_ECOMM) throw RedisError(msg);  // the communicator is gone: the cache is broken
+    return;
+  }
+  if (refund) {  // nobody waits for these
+    done_calls(calls.size());
     return;
   }
   size_t d = 0;
@@ -1455,6 +1495,27 @@ void HipRoutedRateLimitCache::submitter() {
   std::vector<rl_status> out;
   std::vector<uint32_t> thr;
   uint64_t seq = 0;
+  // HIP_REFUND_REJECTED: a request one of whose descriptors came back over its limit is queued as
+  // a control call of the batcher's own, for the next agreement (rl_router_refund there decides
+  // which of its descriptors are owed)
+  auto queue_refund = [&](const PendingCall& c, const rl_status* out) {
+    bool rejected = false;
+    for (size_t i = 0; i < c.prefix.size(); ++i) rejected |= (out[i].code_flags & 0xFFu) == (uint32_t)RL_CODE_OVER_LIMIT;
+    if (!rejected) return;
+    auto rf = std::make_shared<PendingCall>();
+    rf->kind = s_.local_cache && s_.local_cache_freecache ? 7 : 6;
+    rf->now = c.now;
+    rf->hits = c.req->HitsAddend;
+    rf->prefix = c.prefix;
+    rf->blob_bytes = c.blob_bytes;
+    rf->statuses.assign(out, out + c.prefix.size());
+    for (const auto& lim : *c.limits) rf->rule_ids.push_back(lim ? ids_.at(limit_key(*lim)) : RL_NIL_RULE);
+    {
+      std::lock_guard<std::mutex> g(mu_);
+      ++inflight_;
+    }
+    ctl.push_back(std::move(rf));
+  };
   auto finish_one = [&] {
     Step st = std::move(fl.front());
     fl.pop_front();
@@ -1475,6 +1536,7 @@ void HipRoutedRateLimitCache::submitter() {
     size_t d = 0;
     for (size_t r = 0; r < st.calls.size(); ++r) {
       PendingCall& c = *st.calls[r];
+      if (s_.refund_rejected) queue_refund(c, out.data() + d);  // (before the caller is released)
       answer(c, out.data() + d, thr[r]);
       d += c.prefix.size();
     }

@@ -499,6 +499,24 @@ class HipRoutedRateLimitCache : public RateLimitCache {
   std::vector<PeekStatus> Adjust(const RateLimitRequest& request, const std::vector<std::shared_ptr<RateLimit>>& limits,
                                  const std::vector<int32_t>& deltas, bool keep_cache = false);
 
+  // HIP_REFUND_REJECTED (off by default; rl_hip.h "Routed refund"): when a step completes, every
+  // request of it that the limiter rejected is queued as a control call of the batcher's own, with
+  // nobody waiting on it: the request's prefixes, rule ids, time, HitsAddend and statuses. Two
+  // further control kinds carry them, without and with the keep bit (set when the host freecache
+  // model is on, as in the single-engine batcher), counted in every rank's agreement words like the
+  // other kinds. At the agreement they run first, before the callers' Peeks, Forgets, Sets and
+  // Adjusts: every rank's pending ones as one rl_router_refund, as far as one router batch holds
+  // them (the rest waits for the following agreement; a rank with none passes an empty batch). So a
+  // refund is applied at the agreement after its step, not behind the step itself as on the
+  // single-engine batcher: until then the counters hold the rejected request's charge, at most
+  // rule_sync_every x step_us. The trace hook reports each as (the next step's sequence number,
+  // kTraceControl) with a null request. A stop is agreed only when none is pending. With the
+  // option off nothing changes.
+  // refund_flights(): rl_router_refund calls that carried refunds of this rank; refund_failures():
+  // those that were refused or failed (their refunds are dropped: the counters stay charged).
+  uint64_t refund_flights() const { return n_refunds_.load(); }
+  uint64_t refund_failures() const { return n_refund_fail_.load(); }
+
   struct RoutedStats {
     uint64_t steps, empty_steps, rule_syncs, rules, held_calls;
   };
@@ -540,6 +558,7 @@ class HipRoutedRateLimitCache : public RateLimitCache {
   std::vector<rl_rule> pending_;  // new limits seen here, not agreed yet
   std::set<std::pair<uint32_t, uint32_t>> pending_set_;
   std::atomic<uint64_t> n_steps_{0}, n_empty_{0}, n_syncs_{0}, n_rules_{0}, n_held_{0};
+  std::atomic<uint64_t> n_refunds_{0}, n_refund_fail_{0};  // HIP_REFUND_REJECTED: router calls made; refused or failed
   TraceFn trace_;
   bool jitter_ = false;
 };

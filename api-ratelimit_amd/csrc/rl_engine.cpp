@@ -94,7 +94,8 @@ enum KernelId {
   KT_FINGERPRINT, KT_HISTOGRAM, KT_HIST_SCAN, KT_SORT_PASS, KT_SCAN, KT_LEADER, KT_DECIDE, KT_FALLBACK, KT_MEMSET,
   KT_CAND, KT_V4_HIST, KT_V4_SCAN, KT_V4_PLACE, KT_V4_GROUP, KT_RESOLVE, KT_RULE_STATS, KT_CACHE_STATS, KT_CENSUS,
   KT_SET_INDEX, KT_SET_PLAN, KT_SET_APPLY, KT_SET_INDEX_ROUTED, KT_MERGE_PLAN, KT_MERGE_APPLY,
-  KT_ADJUST_INDEX, KT_ADJUST_APPLY, KT_ADJUST_INDEX_ROUTED, KT_ADJUST_PACK, KT_REFUND_MARK, KT_REFUND_INDEX, KT_COUNT
+  KT_ADJUST_INDEX, KT_ADJUST_APPLY, KT_ADJUST_INDEX_ROUTED, KT_ADJUST_PACK, KT_REFUND_MARK, KT_REFUND_INDEX,
+  KT_REFUND_OWED, KT_REFUND_INDEX_ROUTED, KT_COUNT
 };
 const char* const kKernelNames[KT_COUNT] = {"k_fingerprint", "k_histogram", "k_hist_scan", "k_sort_pass", "k_scan",
                                             "k_leader",      "k_decide",    "fallback",    "memset",      "k_cand_state",
@@ -103,7 +104,7 @@ const char* const kKernelNames[KT_COUNT] = {"k_fingerprint", "k_histogram", "k_h
                                             "k_set_index",   "k_set_plan",  "k_set_apply", "k_set_index_routed",
                                             "k_merge_plan",  "k_merge_apply", "k_adjust_index", "k_adjust_apply",
                                             "k_adjust_index_routed", "k_adjust_pack", "k_refund_mark",
-                                            "k_refund_index"};
+                                            "k_refund_index", "k_refund_owed", "k_refund_index_routed"};
 
 enum Mode { MODE_LSD = 1, MODE_LSD_FULL = 2, MODE_V4 = 4 };
 
@@ -215,18 +216,18 @@ struct rl_engine {
     hipStreamWaitEvent(xin, stage_hold[s], 0);
     stage_hold[s] = nullptr;
   }
-  // The plan between rl_set_routed_plan / rl_adjust_routed_plan and its commit. Its index and its
+  // The plan between rl_set_routed_plan / rl_adjust_routed_plan / rl_refund_routed_plan and its commit. Its index and its
   // control block stay in rl_set's scratch, so while one is open the engine refuses what an open
   // restore refuses (quiet, set_busy).
   struct Plan {
-    enum Kind { NONE, SET, ADJUST } kind = NONE;
+    enum Kind { NONE, SET, ADJUST, REFUND } kind = NONE;
     uint32_t n = 0;             // records
     SetScratch set_sc{};        // a set's scratch view
     uint32_t set_gen[8] = {};   // ... and its window generation per region
-    AdjScratch adj_sc{};        // an adjust's index view (its counts wait in the control block)
-    static const char* form(Kind k) { return k == ADJUST ? "adjust" : "set"; }
+    AdjScratch adj_sc{};        // an adjust's or a refund's index view (its counts wait in the control block)
+    static const char* form(Kind k) { return k == ADJUST ? "adjust" : k == REFUND ? "refund" : "set"; }
   } plan;
-  // refuses `what` while a plan is open (planning: in the words of the two plan entry points)
+  // refuses `what` while a plan is open (planning: in the words of the plan entry points)
   int set_busy(const char* what, bool planning = false) {
     if (plan.kind == Plan::NONE) return 0;
     const char* form = Plan::form(plan.kind);
@@ -3359,6 +3360,93 @@ int rl_adjust_routed_commit(rl_engine* e, int apply, rl_adjust_report* report) {
                                     nullptr, 0);
     if (rc) return rc;
     adjust_report(reinterpret_cast<const AdjCtl*>(e->h_set_ctl), rep);
+  }
+  if (report) *report = rep;
+  return 0;
+}
+
+// Routed refund, the engine's pieces (rl_hip.h "Routed refund"). The origin's pass makes the amounts
+// and the rule ids the plain pack sees; the owner's plan is a refund's index over records that
+// arrived from every origin, in rl_set's scratch as an adjust plan's is, and its commit is
+// k_adjust_apply's per-key form.
+int rl_refund_route_owed(rl_engine* e, const rl_batch* b, const rl_status* d_status, uint32_t* d_rule_out,
+                         uint32_t* d_amount, uint32_t* d_counts) {
+  if (!e || !b) return RL_EINVAL;
+  const char* what = "rl_refund_route_owed";
+  // the rej scratch is the flights' own: refused wherever a refund flight could be using it
+  if (e->n_fl) return e->fail(RL_ESTATE, "%s while a batch is in flight (call rl_wait)", what);
+  if (e->restoring) return e->fail(RL_ESTATE, "%s between rl_restore_begin and rl_restore_end", what);
+  if (int rc = e->set_busy(what)) return rc;
+  if (b->n_desc > e->cfg.max_batch_desc || b->n_req > e->cfg.max_batch_req)
+    return e->fail(RL_ECAPACITY, "%s: batch exceeds the engine's capacity (max_batch_desc %u, max_batch_req %u)", what,
+                   e->cfg.max_batch_desc, e->cfg.max_batch_req);
+  if (!d_counts) return e->fail(RL_EINVAL, "%s: null count words", what);
+  if (b->n_desc && (!b->n_req || !b->rule_id || !b->req_of || !b->hits_addend || !d_status || !d_rule_out || !d_amount))
+    return e->fail(RL_EINVAL, "%s: null rule id, request index, hits_addend, status, rule or amount array (or "
+                              "descriptors without requests)", what);
+  hipError_t he = hipMemsetAsync(d_counts, 0, 8, e->stream);
+  if (he != hipSuccess) return e->hip_fail(he, what);
+  if (!b->n_desc) return 0;
+  if (int rc = e->refund_ensure()) return rc;
+  he = hipMemsetAsync(e->d_ref_rej, 0, (size_t)b->n_req * 4, e->stream);
+  if (he != hipSuccess) return e->hip_fail(he, what);
+  // the marking pass with the poison word (0: nothing is in flight) and no batch error word: the
+  // caller vouches for the statuses, and the scratch view is not touched
+  e->timed(KT_REFUND_MARK, [&] {
+    launch_refund_flight(e->stream, *b, d_status, nullptr, 0, 0, e->tab, e->d_ref_rej, nullptr, AdjScratch{}, e->d_poison,
+                         nullptr, 0);
+  });
+  e->timed(KT_REFUND_OWED, [&] {
+    launch_refund_owed(e->stream, *b, d_status, e->d_ref_rej, d_rule_out, d_amount, d_counts);
+  });
+  he = hipGetLastError();
+  if (he != hipSuccess) return e->hip_fail(he, what);
+  return 0;
+}
+
+int rl_refund_routed_plan(rl_engine* e, const void* d_records, uint32_t n, rl_peek_reply* d_reply_or_null) {
+  if (!e) return RL_EINVAL;
+  const char* what = "rl_refund_routed_plan";
+  int rc = plan_enter(e, what, n, n && !d_records ? "record" : nullptr);
+  if (rc) return rc;
+  rl_engine::Plan& p = e->plan;
+  if (n) {
+    const AdjScratch sc = e->adj_view(n);
+    const hipError_t he = e->adjust_index_run(sc, KT_REFUND_INDEX_ROUTED, [&] {
+      launch_refund_index_routed(e->stream, reinterpret_cast<const RRec*>(d_records), n, e->d_rules, e->n_rules, e->tab,
+                                 d_reply_or_null, sc);
+    });
+    if (he != hipSuccess) return e->hip_fail(he, "rl_refund_routed_plan (nothing written)");
+    if ((rc = e->fetch_ctl(e->h_set_ctl, sc.ctl, sizeof(AdjCtl), what, kNothingWritten)) != 0) return rc;
+    const uint32_t err = reinterpret_cast<const AdjCtl*>(e->h_set_ctl)->w[ADJ_ERR][0];
+    if (err & ADJ_ERR_BADREC)
+      return e->fail(RL_EINVAL, "%s: a record's rule id is unknown, its time is above 0xFFFD0000 or its rule word has "
+                                "bits above 16 set (nothing written)", what);
+    if (err) return e->fail(RL_EDEVICE, "%s: the call's index overflowed (nothing written)", what);
+    p.adj_sc = sc;
+  }
+  p.kind = rl_engine::Plan::REFUND;
+  p.n = n;
+  return 0;
+}
+
+int rl_refund_routed_commit(rl_engine* e, int apply, rl_refund_report* report) {
+  if (!e) return RL_EINVAL;
+  if (int rc = e->plan_take(rl_engine::Plan::REFUND)) return rc;
+  if (!apply) return 0;
+  const rl_engine::Plan& p = e->plan;
+  rl_refund_report rep;
+  memset(&rep, 0, sizeof rep);
+  rep.descriptors = p.n;
+  if (p.n) {
+    const int rc = adjust_apply_run(e, "rl_refund_routed_commit", e->tab.local_cache != 0, true, p.adj_sc, nullptr,
+                                    nullptr, 0);
+    if (rc) return rc;
+    const AdjCtl* hc = reinterpret_cast<const AdjCtl*>(e->h_set_ctl);
+    rep.absent = hc->w[ADJ_ABSENT][0];
+    rep.refunded = hc->w[ADJ_APPLIED][0];
+    rep.floored = hc->w[ADJ_FLOORED][0];
+    rep.unfrozen = hc->w[ADJ_UNFROZEN][0];
   }
   if (report) *report = rep;
   return 0;

@@ -31,4 +31,20 @@ void launch_refund_flight(hipStream_t st_, const rl_batch& b, const rl_status* s
                           uint32_t n_rules, uint64_t seed, const TableDesc& tab, uint32_t* rej, uint32_t* amount,
                           const AdjScratch& sc, const uint32_t* poison, const uint32_t* batch_err, int pass);
 
+// The origin side of a routed refund (rl_refund_routed.hip), behind the marking pass
+// (launch_refund_flight's pass 0 over the same rej, with a poison word that reads 0 and no batch
+// error word: only b.n_desc, b.n_req and b.req_of are read and the scratch view is not touched).
+// k_refund_owed: amount[i] and rule_out[i] for every descriptor (rule_out may be b.rule_id), the
+// rejected requests added to counts[0] and the owed descriptors to counts[1] (zeroed on the stream
+// by the caller). Reads rule_id, req_of and hits_addend of the batch. Launches nothing for
+// n_desc == 0.
+void launch_refund_owed(hipStream_t st_, const rl_batch& b, const rl_status* st, const uint32_t* rej, uint32_t* rule_out,
+                        uint32_t* amount, uint32_t* counts);
+// The owner side: the record form of k_refund_index over n routed records (RRec) whose h word is
+// the amount and whose rule word's bit 16 is RL_REFUND_KEEP_CACHE. out: n replies in device memory,
+// or nullptr. The index and the control block (an AdjCtl) are zeroed on the stream by the caller
+// first. A malformed record sets ADJ_ERR_BADREC and indexes nothing. Launches nothing for n == 0.
+void launch_refund_index_routed(hipStream_t st, const RRec* recs, uint32_t n, const DevRule* rules, uint32_t n_rules,
+                                const TableDesc& tab, rl_peek_reply* out, const AdjScratch& sc);
+
 }  // namespace rlhip

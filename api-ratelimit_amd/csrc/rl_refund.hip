@@ -23,11 +23,10 @@
 #include "rl_adjust_key.h"
 #include "rl_peek.h"
 #include "rl_refund.h"
+#include "rl_refund_key.h"
 
 namespace rlhip {
 namespace refund {
-
-constexpr int NT = adjust::NT;
 
 // True when the whole grid leaves (both words are the same for every thread): thread 0 says why.
 // An error word that only asks for the rerun (ERR_FALLBACK, without a bad-input bit: settle()'s
@@ -81,33 +80,6 @@ RL_DEV void block_add4(const bool a, const bool b, const bool c, const bool d, R
                                          : &ctl->rejected[0];
     if (sum) atomicAdd(word, sum);
   }
-}
-
-// One pair's sum into the call's index: adjust_key's insert (rl_adjust_key.h), with the wave's sum
-// and limit complement for one descriptor's. The amounts leave as a negative 64-bit net. The
-// entry's count stays 0: only the record form's applying pass reads it (k_adjust_apply PER_KEY),
-// and on a hot key every atomic here is one more turn at a single L2 address.
-RL_DEV void index_add(const unsigned long long pair, const unsigned long long sum, const uint32_t lim_c,
-                      const AdjScratch& sc) {
-  const uint32_t lg = sc.log2_entries;
-  const uint32_t mask = (1u << lg) - 1u;
-  uint32_t pos = (uint32_t)((pair * K0) >> (64 - lg));
-  for (uint32_t probe = 0; probe <= mask; ++probe) {
-    const unsigned long long old = atomicCAS(&sc.index[pos].pair, 0ull, pair);
-    if (old == 0ull || old == pair) {
-      AdjEntry* e = sc.index + pos;
-      atomicAdd(reinterpret_cast<unsigned long long*>(&e->net), 0ull - sum);
-      atomicMax(&e->lim_c, lim_c);
-      return;
-    }
-    pos = (pos + 1u) & mask;
-  }
-  atomicOr(&sc.ctl->w[ADJ_ERR][0], ADJ_ERR_INDEX);
-}
-
-RL_DEV unsigned long long shfl64(const unsigned long long v, const int lane) {
-  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, lane), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), lane);
-  return (unsigned long long)lo | ((unsigned long long)hi << 32);
 }
 
 // A thread past n_desc reads descriptor n_desc - 1 and uses nothing of it (`live`): it stays for
@@ -178,7 +150,7 @@ __global__ __launch_bounds__(NT) void k_refund_index(const DevBatch in, const rl
     const bool mine = pair == lp;  // (lp != 0: never a lane without a pair)
     const unsigned long long grp = __ballot(mine);
     if (grp == (1ull << leader)) {
-      if (mine) index_add(pair, (unsigned long long)amt, lim_c, sc);
+      if (mine) index_add(pair, (unsigned long long)amt, lim_c, 0u, sc);
     } else {
       unsigned long long sum = mine ? (unsigned long long)amt : 0ull;
       uint32_t lc = mine ? lim_c : 0u;
@@ -188,7 +160,7 @@ __global__ __launch_bounds__(NT) void k_refund_index(const DevBatch in, const rl
         const uint32_t olc = (uint32_t)__shfl((int)lc, (int)(lane ^ (uint32_t)o));
         lc = olc > lc ? olc : lc;
       }
-      if (lane == (uint32_t)leader) index_add(pair, sum, lc, sc);
+      if (lane == (uint32_t)leader) index_add(pair, sum, lc, 0u, sc);
     }
     todo &= ~grp;
   }

@@ -55,6 +55,7 @@
 #include "rl_hip.h"
 #include "rl_internal.h"
 #include "rl_adjust.h"
+#include "rl_refund.h"
 #include "rl_set.h"
 
 using namespace rlhip;
@@ -323,22 +324,33 @@ struct EmuXport : Xport {
   }
 };
 
-// The routed by-key calls (rl_router_peek / _forget / _set / _adjust): one origin / exchange /
-// owner / reply sequence, differing in the owner's work (and, for a set, the values beside the
-// records; for a set and an adjust, the plan-status exchange ahead of any write).
-enum ByKeyOp { OP_PEEK, OP_FORGET, OP_SET, OP_ADJUST };
+// The routed by-key calls (rl_router_peek / _forget / _set / _adjust / _refund): one origin /
+// exchange / owner / reply sequence, differing in the owner's work (and, for a set, the values
+// beside the records; for a set, an adjust and a refund, the plan-status exchange ahead of any
+// write; for a refund, the origin's pass that decides which descriptors travel).
+enum ByKeyOp { OP_PEEK, OP_FORGET, OP_SET, OP_ADJUST, OP_REFUND };
 const char* op_name(ByKeyOp op) {
-  return op == OP_ADJUST ? "rl_router_adjust"
+  return op == OP_REFUND ? "rl_router_refund"
+         : op == OP_ADJUST ? "rl_router_adjust"
          : op == OP_SET  ? "rl_router_set"
                          : op == OP_FORGET ? "rl_router_forget" : "rl_router_peek";
 }
-inline bool two_phase(ByKeyOp op) { return op == OP_SET || op == OP_ADJUST; }
+inline bool two_phase(ByKeyOp op) { return op == OP_SET || op == OP_ADJUST || op == OP_REFUND; }
 // What an adjust carries beside the batches: one delta array, one flags word and one report per
 // engine passed at create.
 struct AdjustArgs {
   const int32_t* const* delta;
   const uint32_t* flags;
   rl_adjust_report* const* report;
+};
+
+// What a refund carries beside the batches: one status array, one flags word, one amount array (or
+// null) and one report (or null) per engine passed at create.
+struct RefundArgs {
+  const rl_status* const* status;
+  const uint32_t* flags;
+  uint32_t* const* amount;
+  rl_refund_report* const* report;
 };
 
 // One owner run: consecutive origins' records (compact by origin) whose times fit one engine batch.
@@ -447,6 +459,15 @@ struct Shard {
   int32_t* ad_h = nullptr;
   int32_t* ad_d = nullptr;
   rl_adjust_report ad_rep{};
+  // routed refund (allocated at its first call): the origin's statuses (pinned + device staging),
+  // its rej scratch (one word per request, and a zero word), the amounts with the two count words behind them
+  // (device, and a pinned copy); the commit's report until the call is known to have succeeded
+  rl_status* rf_h_st = nullptr;
+  rl_status* rf_d_st = nullptr;
+  uint32_t* rf_d_rej = nullptr;
+  uint32_t* rf_d_amt = nullptr;  // [max_desc] amounts, then [2] counts
+  uint32_t* rf_h_amt = nullptr;
+  rl_refund_report rf_rep{};
 };
 
 struct StepSlot {
@@ -563,19 +584,23 @@ struct rl_router {
   void pack(uint32_t s, uint32_t k, bool plain = false);
   int peek_validate(const rl_batch& b, uint32_t n_rules, std::string& why) const;
   int peek_alloc(Shard& S);
-  int peek_stage(uint32_t s, uint32_t k, const rl_batch& hb, rl_batch& db);
+  int peek_stage(uint32_t s, uint32_t k, const rl_batch& hb, rl_batch& db, bool hits = false);
   int set_validate(const Shard& S, const rl_batch& b, const rl_peek_reply* values, std::string& why) const;
   int set_alloc(Shard& S);
+  int refund_alloc(Shard& S);
   int peek(const rl_batch* batches, rl_peek_reply* const* out, ByKeyOp op, const rl_peek_reply* const* values = nullptr,
-           const AdjustArgs* adj = nullptr);
+           const AdjustArgs* adj = nullptr, const RefundArgs* ref = nullptr);
   int adjust_alloc(Shard& S);
-  // the owner's two phases of a set or an adjust
+  // the owner's two phases of a set, an adjust or a refund
   int owner_plan(Shard& S, ShardStep& t, ByKeyOp op) {
-    return op == OP_SET ? rl_set_routed_plan(S.e, t.recv, S.sv_recv, t.n_in, S.pk_reply)
-                        : rl_adjust_routed_plan(S.e, t.recv, t.n_in, S.pk_reply);
+    return op == OP_SET      ? rl_set_routed_plan(S.e, t.recv, S.sv_recv, t.n_in, S.pk_reply)
+           : op == OP_REFUND ? rl_refund_routed_plan(S.e, t.recv, t.n_in, S.pk_reply)
+                             : rl_adjust_routed_plan(S.e, t.recv, t.n_in, S.pk_reply);
   }
   int owner_commit(Shard& S, ByKeyOp op, int apply) {
-    return op == OP_SET ? rl_set_routed_commit(S.e, apply) : rl_adjust_routed_commit(S.e, apply, &S.ad_rep);
+    return op == OP_SET      ? rl_set_routed_commit(S.e, apply)
+           : op == OP_REFUND ? rl_refund_routed_commit(S.e, apply, &S.rf_rep)
+                             : rl_adjust_routed_commit(S.e, apply, &S.ad_rep);
   }
   int peek_coll(uint32_t k, rl_peek_reply* const* out, ByKeyOp op);
   int peek_local(uint32_t k, rl_peek_reply* const* out, ByKeyOp op);
@@ -612,6 +637,11 @@ void rl_router::free_all() {
     if (s.sv_h) (void)hipHostFree(s.sv_h);
     if (s.ad_d) (void)hipFree(s.ad_d);
     if (s.ad_h) (void)hipHostFree(s.ad_h);
+    if (s.rf_d_st) (void)hipFree(s.rf_d_st);
+    if (s.rf_h_st) (void)hipHostFree(s.rf_h_st);
+    if (s.rf_d_rej) (void)hipFree(s.rf_d_rej);
+    if (s.rf_d_amt) (void)hipFree(s.rf_d_amt);
+    if (s.rf_h_amt) (void)hipHostFree(s.rf_h_amt);
     if (s.d_hot) (void)hipFree(s.d_hot);
     if (s.h_hot) (void)hipHostFree(s.h_hot);
     if (s.ev_hot) (void)hipEventDestroy(s.ev_hot);
@@ -1602,8 +1632,8 @@ int rl_router::peek_alloc(Shard& S) {
 }
 
 // A validated host batch -> pinned staging -> device on the shard's origin stream, in the step's
-// staging layout; hits_addend staged as zeros, no jitter.
-int rl_router::peek_stage(uint32_t s, uint32_t k, const rl_batch& b, rl_batch& d) {
+// staging layout; hits_addend staged as zeros (hits: the batch's own, for a refund), no jitter.
+int rl_router::peek_stage(uint32_t s, uint32_t k, const rl_batch& b, rl_batch& d, bool hits) {
   Shard& S = sh[s];
   const bool host = (cfg.flags & RL_ROUTER_HOST) != 0;
   uint8_t* h = host ? S.st[k].hs.h_in : S.pk_h_in;
@@ -1613,7 +1643,7 @@ int rl_router::peek_stage(uint32_t s, uint32_t k, const rl_batch& b, rl_batch& d
   struct Arr { const void* src; size_t o, n; } arrs[] = {
       {b.prefix_blob, 0, b.blob_bytes}, {b.prefix_off, o_off, ((size_t)b.n_desc + 1) * 4},
       {b.rule_id, o_rule, (size_t)b.n_desc * 4}, {b.req_of, o_req, (size_t)b.n_desc * 4},
-      {b.now, o_now, (size_t)b.n_req * 8}, {nullptr, o_hits, (size_t)b.n_req * 4}};
+      {b.now, o_now, (size_t)b.n_req * 8}, {hits ? b.hits_addend : nullptr, o_hits, (size_t)b.n_req * 4}};
   for (auto& a : arrs) {
     if (a.n && a.src) memcpy(h + a.o, a.src, a.n);
     else if (a.n) memset(h + a.o, 0, a.n);
@@ -1688,10 +1718,30 @@ int rl_router::adjust_alloc(Shard& S) {
   return he == hipSuccess ? 0 : RL_EHIP;
 }
 
+int rl_router::refund_alloc(Shard& S) {
+  if (S.rf_h_st && S.rf_d_st && S.rf_d_rej && S.rf_d_amt && S.rf_h_amt) return 0;
+  const size_t n = cfg.max_desc ? cfg.max_desc : 1u;
+  hipError_t he = hipSuccess;
+  if (!S.rf_h_st) he = hipHostMalloc(&S.rf_h_st, n * sizeof(rl_status), hipHostMallocDefault);
+  if (he == hipSuccess && !S.rf_d_st) he = hipMalloc(&S.rf_d_st, n * sizeof(rl_status));
+  if (he == hipSuccess && !S.rf_d_rej) {  // (n_req <= max_desc) and one word behind that stays 0
+    he = hipMalloc(&S.rf_d_rej, (n + 1) * 4);
+    if (he == hipSuccess) he = hipMemset(S.rf_d_rej + n, 0, 4);
+    if (he != hipSuccess && S.rf_d_rej) {
+      (void)hipFree(S.rf_d_rej);
+      S.rf_d_rej = nullptr;
+    }
+  }
+  if (he == hipSuccess && !S.rf_d_amt) he = hipMalloc(&S.rf_d_amt, (n + 2) * 4);
+  if (he == hipSuccess && !S.rf_h_amt) he = hipHostMalloc(&S.rf_h_amt, (n + 2) * 4, hipHostMallocDefault);
+  return he == hipSuccess ? 0 : RL_EHIP;
+}
+
 // The origin half of every by-key call, then the transport's half. values: a set's, per engine;
-// adj: an adjust's deltas, flags and reports, per engine.
+// adj: an adjust's deltas, flags and reports, per engine; ref: a refund's statuses, flags, amounts
+// and reports, per engine.
 int rl_router::peek(const rl_batch* batches, rl_peek_reply* const* out, ByKeyOp op,
-                    const rl_peek_reply* const* values, const AdjustArgs* adj) {
+                    const rl_peek_reply* const* values, const AdjustArgs* adj, const RefundArgs* ref) {
   const char* what = op_name(op);
   if (broken) return fail(RL_ECOMM, "the router's communicator was aborted after a transport failure");
   if (done != seq) return fail(RL_ESTATE, "%s with a routed step in flight: call rl_router_wait", what);
@@ -1722,10 +1772,23 @@ int rl_router::peek(const rl_batch* batches, rl_peek_reply* const* out, ByKeyOp 
       rc = RL_EINVAL;
       t.msg = "unknown flag bits";
     }
+    if (!rc && op == OP_REFUND && batches[s].n_desc && !ref->status[s]) {
+      rc = RL_EINVAL;
+      t.msg = "null status array";
+    }
+    if (!rc && op == OP_REFUND && batches[s].n_desc && !batches[s].hits_addend) {
+      rc = RL_EINVAL;
+      t.msg = "null hits_addend";
+    }
+    if (!rc && op == OP_REFUND && (ref->flags[s] & ~(uint32_t)RL_REFUND_KEEP_CACHE)) {
+      rc = RL_EINVAL;
+      t.msg = "unknown flag bits";
+    }
     if (!rc && (rc = peek_alloc(S))) t.msg = "reply buffer / staging allocation failed";
     if (!rc && op == OP_SET && (rc = set_alloc(S))) t.msg = "value buffer / staging allocation failed";
     if (!rc && op == OP_ADJUST && (rc = adjust_alloc(S))) t.msg = "delta staging allocation failed";
-    if (!rc && (rc = peek_stage(s, k, batches[s], t.b))) t.msg = "host staging copy failed";
+    if (!rc && op == OP_REFUND && (rc = refund_alloc(S))) t.msg = "status staging / scratch allocation failed";
+    if (!rc && (rc = peek_stage(s, k, batches[s], t.b, op == OP_REFUND))) t.msg = "host staging copy failed";
     if (!rc && op == OP_SET && batches[s].n_desc) {
       const size_t nb = (size_t)batches[s].n_desc * sizeof(rl_peek_reply);
       memcpy(S.sv_h, values[s], nb);
@@ -1742,9 +1805,41 @@ int rl_router::peek(const rl_batch* batches, rl_peek_reply* const* out, ByKeyOp 
         t.msg = "delta staging copy failed";
       }
     }
+    if (!rc && op == OP_REFUND && batches[s].n_desc) {
+      // The statuses in, then the marking pass and k_refund_owed on the origin stream: the amounts,
+      // and over the staged rule ids the ids the pack sees (an unowed descriptor's is nil: it stays
+      // at home). The marking pass reads the zero word behind rej where a flight's reads the engine's
+      // poison word (d_ok exists on the collective transports only).
+      const rl_batch& b = t.b;
+      const size_t nb = (size_t)b.n_desc * sizeof(rl_status);
+      memcpy(S.rf_h_st, ref->status[s], nb);
+      hipError_t he = hipMemcpyAsync(S.rf_d_st, S.rf_h_st, nb, hipMemcpyHostToDevice, S.os);
+      if (he == hipSuccess) he = hipMemsetAsync(S.rf_d_rej, 0, (size_t)b.n_req * 4, S.os);
+      if (he == hipSuccess) he = hipMemsetAsync(S.rf_d_amt + cfg.max_desc, 0, 8, S.os);
+      if (he == hipSuccess) {
+        launch_refund_flight(S.os, b, S.rf_d_st, nullptr, 0, 0, TableDesc{}, S.rf_d_rej, nullptr, AdjScratch{},
+                             S.rf_d_rej + (cfg.max_desc ? cfg.max_desc : 1u), nullptr, 0);
+        launch_refund_owed(S.os, b, S.rf_d_st, S.rf_d_rej, const_cast<uint32_t*>(b.rule_id), S.rf_d_amt,
+                           S.rf_d_amt + cfg.max_desc);
+        he = hipGetLastError();
+      }
+      if (he == hipSuccess)  // the amounts and the two counts to the host, for the caller and the report
+        he = hipMemcpyAsync(S.rf_h_amt, S.rf_d_amt, (size_t)b.n_desc * 4, hipMemcpyDeviceToHost, S.os);
+      if (he == hipSuccess)
+        he = hipMemcpyAsync(S.rf_h_amt + cfg.max_desc, S.rf_d_amt + cfg.max_desc, 8, hipMemcpyDeviceToHost, S.os);
+      if (he != hipSuccess) {
+        rc = RL_EHIP;
+        t.msg = std::string("status staging / owed pass: ") + hipGetErrorString(he);
+      }
+    }
     if (rc) t.b = rl_batch{};
     t.rc_pack = rc;
     pack(s, k, true);
+    if (op == OP_REFUND && !t.rc_pack && t.b.n_desc) {  // the amounts and the keep bit into the owed records
+      launch_adjust_pack(S.os, t.b.n_desc, cfg.max_desc * cfg.n_shards, t.pb.perm, t.b.rule_id,
+                         reinterpret_cast<const int32_t*>(S.rf_d_amt), ref->flags[s] & RL_REFUND_KEEP_CACHE, t.pb.send);
+      (void)hipGetLastError();  // (a failed launch shows at the stream's next wait)
+    }
     if (op == OP_ADJUST && !t.rc_pack && t.b.n_desc) {  // the deltas and the keep bit into the records, behind the pack
       launch_adjust_pack(S.os, t.b.n_desc, cfg.max_desc * cfg.n_shards, t.pb.perm, t.b.rule_id, S.ad_d,
                          adj->flags[s] & RL_ADJUST_KEEP_CACHE, t.pb.send);
@@ -1760,6 +1855,20 @@ int rl_router::peek(const rl_batch* batches, rl_peek_reply* const* out, ByKeyOp 
   if (!rc && op == OP_ADJUST && adj->report)  // what each engine did as an owner
     for (uint32_t s = 0; s < nl; ++s)
       if (adj->report[s]) *adj->report[s] = sh[s].ad_rep;
+  if (!rc && op == OP_REFUND) {
+    // each engine's amounts, and its report: what it saw as an origin, what it did as an owner
+    for (uint32_t s = 0; s < nl; ++s) {
+      const Shard& S = sh[s];
+      const uint32_t n = S.st[k].b.n_desc;
+      if (ref->amount && ref->amount[s] && n) memcpy(ref->amount[s], S.rf_h_amt, (size_t)n * 4);
+      if (!ref->report || !ref->report[s]) continue;
+      rl_refund_report r = S.rf_rep;
+      r.descriptors = n;
+      r.rejected_req = n ? S.rf_h_amt[cfg.max_desc] : 0u;
+      r.skipped = n ? n - S.rf_h_amt[cfg.max_desc + 1] : 0u;
+      *ref->report[s] = r;
+    }
+  }
   return rc;
 }
 
@@ -2074,6 +2183,14 @@ int rl_router_adjust(rl_router* r, const rl_batch* host_batches, const int32_t* 
   if (!r || !host_batches || !delta || !flags) return RL_EINVAL;
   const AdjustArgs a{delta, flags, report_or_null};
   return r->peek(host_batches, out_or_null, OP_ADJUST, nullptr, &a);
+}
+
+int rl_router_refund(rl_router* r, const rl_batch* host_batches, const rl_status* const* status, const uint32_t* flags,
+                     uint32_t* const* amount_or_null, rl_peek_reply* const* out_or_null,
+                     rl_refund_report* const* report_or_null) {
+  if (!r || !host_batches || !status || !flags) return RL_EINVAL;
+  const RefundArgs a{status, flags, amount_or_null, report_or_null};
+  return r->peek(host_batches, out_or_null, OP_REFUND, nullptr, nullptr, &a);
 }
 
 int rl_router_unique_id(uint8_t* id_out) {

@@ -338,6 +338,11 @@ ABI = [
     ("rl_adjust_routed_commit", [C.c_void_p, C.c_int, C.POINTER(RlAdjustReport)], C.c_int),
     ("rl_router_adjust", [C.c_void_p, C.POINTER(RlBatch), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32),
                           C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)], C.c_int),
+    ("rl_refund_route_owed", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    ("rl_refund_routed_plan", [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p], C.c_int),
+    ("rl_refund_routed_commit", [C.c_void_p, C.c_int, C.POINTER(RlRefundReport)], C.c_int),
+    ("rl_router_refund", [C.c_void_p, C.POINTER(RlBatch), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32),
+                          C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)], C.c_int),
     ("rl_resize", [C.c_void_p, C.POINTER(C.c_uint32)], C.c_int),
     ("rl_rule_stats_add_device", [C.c_void_p, C.POINTER(RlBatch), C.c_void_p], C.c_int),
     ("rl_rule_stats_read", [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32], C.c_int),
@@ -990,6 +995,39 @@ class Engine:
                     "rl_adjust_routed_commit")
         return {f: int(getattr(rep, f)) for f in ADJUST_REPORT_FIELDS}
 
+    # ---- routed refund (rl_hip.h "Routed refund") ----
+    def refund_route_owed(self, n_desc: int, n_req: int, blob_bytes: int, ptrs, status_ptr: int, rule_out_ptr: int,
+                          amount_ptr: int, counts_ptr: int):
+        """rl_refund_route_owed: the origin's pass of a routed refund over a device batch (ptrs = blob,
+        off, rule, req_of, now, hits; rule, req_of and hits are read) and its n_desc statuses at
+        status_ptr: the amount owed per descriptor (uint32, 0: not owed) to amount_ptr, the rule id
+        the plain pack is to see (the descriptor's own when owed, else NIL_RULE) to rule_out_ptr, which
+        may be the batch's own rule array, and the numbers of rejected requests and owed descriptors
+        to the two uint32 at counts_ptr. All device memory, asynchronous on the engine stream."""
+        s = RlBatch()
+        s.n_desc, s.n_req, s.blob_bytes, s.reserved = n_desc, n_req, blob_bytes, 0
+        _set_ptrs(s, ptrs)
+        self._check(self.lib.rl_refund_route_owed(self.h, C.byref(s), status_ptr or None, rule_out_ptr or None,
+                                                  amount_ptr or None, counts_ptr or None), "rl_refund_route_owed")
+
+    def refund_routed_plan(self, rec_ptr: int, n: int, reply_ptr: int = 0):
+        """rl_refund_routed_plan: phase 1 of a routed refund over n routed records (ROUTE_RECORD_BYTES
+        each; h is the uint32 amount, bit 16 of the rule word keep_cache) in device memory: the
+        replies (the state before the call) to reply_ptr when it is not 0, and the call's index.
+        Synchronous; on return a plan is open and nothing has been written, or RedisError and no plan
+        is open."""
+        self._check(self.lib.rl_refund_routed_plan(self.h, rec_ptr or None, n, reply_ptr or None),
+                    "rl_refund_routed_plan")
+
+    def refund_routed_commit(self, apply: bool = True) -> dict:
+        """rl_refund_routed_commit: phase 2. apply: the applying pass over the plan's index; else drop
+        it. Returns the report as a dict of REFUND_REPORT_FIELDS, the owner's fields filled (all 0 for
+        a dropped plan)."""
+        rep = RlRefundReport()
+        self._check(self.lib.rl_refund_routed_commit(self.h, int(bool(apply)), C.byref(rep)),
+                    "rl_refund_routed_commit")
+        return {f: int(getattr(rep, f)) for f in REFUND_REPORT_FIELDS}
+
     def route_unpack_peek(self, n_desc: int, perm_ptr: int, back_ptr: int, out_ptr: int):
         """rl_route_unpack_peek: out[i] = back[perm[i]] (NIL where perm[i] is ROUTE_LOCAL), all in
         device memory, asynchronous on the engine stream."""
@@ -1216,7 +1254,7 @@ class Engine:
         self._check(self.lib.rl_set_timing(self.h, int(on)), "rl_set_timing")
 
     def kernel_times(self) -> dict:
-        cap = 32
+        cap = 64  # (the engine has 32 timing slots)
         names = (C.c_char_p * cap)()
         ms = (C.c_double * cap)()
         cnt = (C.c_uint64 * cap)()
@@ -1474,6 +1512,47 @@ class Router:
         self._check(self.lib.rl_router_adjust(self.h, arr, da, fl, o, ra), "rl_router_adjust")
         return ([outs[i][:b.n_desc] for i, b in enumerate(batches)] if want_out else None,
                 [{f: int(getattr(reps[i], f)) for f in ADJUST_REPORT_FIELDS} for i in range(self.n)])
+
+    def refund(self, batches, statuses, keep_cache=False, want_out: bool = True):
+        """rl_router_refund: per engine passed at create a host Batch (hits_addend is read) and the
+        statuses a step returned for it (STATUS_DTYPE, one per descriptor): every counted descriptor
+        of a rejected request is given max(1, hits_addend) back at the owner of its key, summed per
+        (string, store) over every origin and floored once; all owners or none. Only the owed
+        descriptors travel. keep_cache: a bool, or one bool per batch. Collective like adjust (an
+        empty Batch where a rank refunds nothing). Returns (one uint32 array per batch: what each
+        descriptor was owed, 0 when skipped; one PEEK_DTYPE array per batch: the state before the call
+        for an owed descriptor, PEEK_NIL for any other, or None; one report dict per engine: its
+        origin fields descriptors / rejected_req / skipped and its owner fields absent / refunded /
+        floored / unfrozen)."""
+        keeps = [bool(keep_cache)] * self.n if isinstance(keep_cache, (bool, np.bool_)) else [bool(k) for k in keep_cache]
+        if len(keeps) != self.n or len(batches) != self.n or len(statuses) != self.n:
+            raise ValueError(f"rl_router_refund: needs {self.n} batches, status arrays and keep_cache flags")
+        sts = []
+        for b, st in zip(batches, statuses):
+            a = np.asarray(st)
+            if a.dtype != STATUS_DTYPE:
+                raise ValueError("rl_router_refund: a status array is not of STATUS_DTYPE")
+            if a.shape != (b.n_desc,):
+                raise ValueError(f"rl_router_refund: {a.shape[0] if a.ndim == 1 else a.shape} statuses for "
+                                 f"{b.n_desc} descriptors")
+            sts.append(np.ascontiguousarray(a))
+        structs = [_batch_struct(b) for b in batches]
+        for s in structs:  # (not read by the call)
+            s.ttl_jitter = None
+        arr = (RlBatch * self.n)(*structs)
+        pads = [a if a.shape[0] else np.zeros(1, STATUS_DTYPE) for a in sts]
+        sa = (C.c_void_p * self.n)(*[x.ctypes.data for x in pads])
+        fl = (C.c_uint32 * self.n)(*[REFUND_KEEP_CACHE if k else 0 for k in keeps])
+        amts = [np.zeros(max(1, b.n_desc), np.uint32) for b in batches]
+        aa = (C.c_void_p * self.n)(*[x.ctypes.data for x in amts])
+        outs = [np.zeros(max(1, b.n_desc), PEEK_DTYPE) for b in batches]
+        o = (C.c_void_p * self.n)(*[x.ctypes.data for x in outs]) if want_out else None
+        reps = (RlRefundReport * self.n)()
+        ra = (C.c_void_p * self.n)(*[C.addressof(reps[i]) for i in range(self.n)])
+        self._check(self.lib.rl_router_refund(self.h, arr, sa, fl, aa, o, ra), "rl_router_refund")
+        return ([amts[i][:b.n_desc] for i, b in enumerate(batches)],
+                [outs[i][:b.n_desc] for i, b in enumerate(batches)] if want_out else None,
+                [{f: int(getattr(reps[i], f)) for f in REFUND_REPORT_FIELDS} for i in range(self.n)])
 
     def allgather_host(self, data: bytes, n_ranks: int) -> list:
         """rl_router_allgather_host: every rank's `data` (the same length everywhere), in rank

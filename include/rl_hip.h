@@ -1212,7 +1212,9 @@ int rl_router_set(rl_router* r, const rl_batch* host_batches, const rl_peek_repl
  * nothing else of the send buffer is touched. Ordered on the engine stream, returns at once. Reads
  * n_desc and rule_id of the batch. RL_EINVAL for a null array with n_desc > 0 or a flag bit other
  * than RL_ADJUST_KEEP_CACHE. With this the records alone carry the call: there is no second value
- * exchange as a set has.
+ * exchange as a set has. A routed refund ("Routed refund" below) passes its uint32 amounts as the
+ * delta words and RL_REFUND_KEEP_CACHE (the same bit) as the flag: the word's 32 bits are stored
+ * whole, so the refund needs no pack kernel of its own.
  * rl_adjust_routed_plan: phase 1 over n such records. Identity and lookup are rl_peek_routed's (the
  * record's prefix lanes, time and rule), then rl_adjust's own index step: a found record adds
  * (int32_t)h, its rule's limit and one to its (string, store) pair's entry of the call's scratch
@@ -1279,6 +1281,93 @@ int rl_adjust_routed_commit(rl_engine* e, int apply, rl_adjust_report* report_or
 int rl_router_adjust(rl_router* r, const rl_batch* host_batches, const int32_t* const* delta,
                      const uint32_t* flags /* one per engine passed at create */,
                      rl_peek_reply* const* out_or_null, rl_adjust_report* const* report_or_null);
+
+/* ---- Routed refund -----------------------------------------------------------
+ * "Refund" above where the keys are spread over the shards of a router. The rank that sees a
+ * request's verdict is in general not the owner of its keys, and rl_refund_behind refuses a routed
+ * flight (its statuses are made at the origin, its counters live elsewhere). rl_router_adjust cannot
+ * stand in: its deltas are int32, it looks up every descriptor, and the host would have to rebuild
+ * the rule for which descriptors are owed from statuses it read back. Here that rule runs on the
+ * origin's device, only the owed descriptors travel, and the amount is a full uint32 end to end.
+ *
+ * Engine level (device memory):
+ * rl_refund_route_owed: the origin's pass over a device batch and its n_desc statuses. Ordered on
+ * the engine stream, returns at once. Two kernels with the kernel boundary between them: the
+ * refund's marking pass (an over-limit descriptor marks its request in the refund's own scratch,
+ * 4 B x max_batch_req), then one lane per descriptor, streaming (no rule entry, no prefix byte and no
+ * table slot is read): d_amount[i] = max(1, hits_addend[req_of[i]]) when descriptor i is owed, else
+ * 0, where owed is rl_refund_pipelined's rule exactly (its request has a descriptor of code
+ * RL_CODE_OVER_LIMIT, its rule is not RL_NIL_RULE, its status carries no RL_FLAG_LOCAL_CACHE_HIT);
+ * d_rule_out[i] = rule_id[i] when owed, else RL_NIL_RULE (a descriptor whose request index is not
+ * below n_req keeps its rule id, so that the pack behind refuses the batch). d_rule_out may be the
+ * batch's own rule_id array: every lane reads its word before it writes it. d_counts[0] receives
+ * the number of rejected requests and d_counts[1] the number of owed descriptors; both words are
+ * zeroed on the stream by the call. rl_route_pack_strided of the batch with d_rule_out as its rule
+ * array then leaves every unowed descriptor at home (perm[i] == RL_ROUTE_LOCAL): no record, no
+ * lookup and no byte on the wire is spent on it. Behind that pack, rl_route_pack_adjust is passed
+ * d_amount as its delta words (and the batch with d_rule_out as its rule array): it stores the
+ * word's 32 bits whole into h and rule | keep << 16 beside it, so no pack kernel of the refund's own
+ * exists. RL_EINVAL for a null array with n_desc > 0 (hits_addend is read) or null d_counts;
+ * RL_ECAPACITY for n_desc / n_req over the engine's maxima; RL_ESTATE while a batch or flight is in
+ * flight, a restore is open or a plan is open (the scratch is shared); all with nothing launched.
+ * n_desc == 0 launches nothing and writes zeros to d_counts.
+ * rl_refund_routed_plan: phase 1 over n such records; rl_adjust_routed_plan's lifecycle, return
+ * codes and gates, word for word. Identity and lookup are rl_peek_routed's at the record's own time;
+ * replies (the state before the call, for every duplicate; RL_PEEK_BAD and zeros for a malformed
+ * record) go to d_reply when it is not NULL. Where the counter is found the amount is the record's h
+ * as a full uint32: it never passes through an int32. The lanes of a wave that hold one (string,
+ * store) pair combine before the atomics, as the refund flight's do: the 64-bit sum of the amounts,
+ * the smallest limit, and the number of the pair's records that came without the keep bit. A record
+ * is malformed as an adjust's is (rule id, time above 0xFFFD0000, a bit 17..31 of the rule word):
+ * RL_EINVAL, nothing indexed. Nothing is written to the table. A refund plan is a third kind of
+ * plan: rl_set_routed_commit or rl_adjust_routed_commit on it returns RL_ESTATE and leaves it open,
+ * and rl_refund_routed_commit on a set or adjust plan likewise. n == 0 opens an empty plan. The call
+ * synchronises the engine stream; the plan lives in rl_set's scratch.
+ * rl_refund_routed_commit: phase 2. apply == 0 drops the plan. Otherwise rl_adjust's applying pass
+ * runs in its per-key form: new = max(0, count - sum) once per pair, the expiry untouched; a pair
+ * with new <= its smallest limit and a found record without the keep bit gets its local-cache
+ * deadline cleared (when the local cache is on). *report holds the owner's fields: descriptors = n,
+ * rejected_req = skipped = 0, absent, refunded, floored, unfrozen, with descriptors == absent +
+ * refunded.
+ *
+ * rl_router_refund: rl_router_adjust's contract. Collective; one batch (hits_addend is read), one
+ * status array (n_desc statuses, as the step returned them), one flags word, and one amount array,
+ * output and report (each or NULL, and the three pointer arrays themselves may be NULL) per engine
+ * passed at create; host memory, synchronous; a rank with nothing to refund passes n_desc == 0;
+ * RL_ESTATE before any collective while a step is in flight; all owners or none.
+ *   1. Origin: rl_router_peek's refusals, plus RL_EINVAL for a null status array or null hits_addend
+ *      with n_desc > 0 or a flag bit other than RL_REFUND_KEEP_CACHE; each travels as this origin's
+ *      status in the counts exchange. The batch (hits_addend really staged this time) and the
+ *      statuses are staged (20 B x max_desc of pinned plus device memory, and the origin pass's
+ *      scratch and amounts, allocated at the first call); the origin runs the two kernels of
+ *      rl_refund_route_owed, the plain pack with the rewritten rules, and the amount and keep pack.
+ *   2. Counts, then records: one all-to-all-v. No values travel.
+ *   3. Every owner runs rl_refund_routed_plan over everything it received. The plan codes go to
+ *      every rank; any non-zero code makes every owner drop its plan: the failing rank returns its
+ *      code and the others RL_EPEER (local transport: the first failing shard's code). Nothing is
+ *      written anywhere and every output is untouched.
+ *   4. Every owner commits; the replies and the commit status return by the reverse exchange and
+ *      the origin unpacks them (rl_route_unpack_peek).
+ * Semantics: the amounts of one (string, store) pair are summed over all owed descriptors of all
+ * origins in 64 bits and applied once, floored at 0: a counter of 9 owed 6 by origin 0 and 6 by
+ * origin 1 ends at 0, floored once, in any order. amount[s][i] is what descriptor i was owed, 0
+ * when skipped. out[s][i] is the state before the call for an owed descriptor and {0, 0, 0,
+ * RL_PEEK_NIL} for any other: it was not asked. *report[s] holds engine s's origin fields
+ * (descriptors, rejected_req, skipped: of the batch it passed) and its owner fields (absent,
+ * refunded, floored, unfrozen: of the records it received). The lone engine's identity
+ * descriptors == skipped + absent + refunded therefore does not hold per report; over the world,
+ * the sum of descriptors - skipped equals the sum of absent + refunded.
+ * The step clock, RL_ELATE, the hot sets and rl_router_stats do not move; rule stats, cache stats
+ * and occupancy are untouched as for an adjust; the refunded step's statuses are not rewritten.
+ * Out of scope: a refund while steps are in flight, a device-memory form of the router call, a
+ * compact wire form. */
+int rl_refund_route_owed(rl_engine* e, const rl_batch* device_batch, const rl_status* d_status, uint32_t* d_rule_out,
+                         uint32_t* d_amount, uint32_t* d_counts /* [2] */);
+int rl_refund_routed_plan(rl_engine* e, const void* d_records, uint32_t n, rl_peek_reply* d_reply_or_null);
+int rl_refund_routed_commit(rl_engine* e, int apply, rl_refund_report* report_or_null);
+int rl_router_refund(rl_router* r, const rl_batch* host_batches, const rl_status* const* status,
+                     const uint32_t* flags /* one per engine passed at create */, uint32_t* const* amount_or_null,
+                     rl_peek_reply* const* out_or_null, rl_refund_report* const* report_or_null);
 
 /* ---- Rule stats: per-rule stat counters summed on the device ---------------
  * The reference keeps four counters per limit, <FullKey>.total_hits / .over_limit / .near_limit /
